@@ -29,10 +29,22 @@ counters with rpkt_gpu_flow_reduce (RCCL).  The timed region is bracketed by
 barrier + synchronize and the max over ranks is reported.  At N > 1 the default legs are
 the headline, config 4 and the strong-scaling legs only (LEG_DEFAULTS, --all-legs).
 
-Output: rank 0 prints ONE compact JSON line (< 8,000 bytes: the contract keys, the main
-leg's roofline and CPU baseline, per extra leg its kernel/step times, roofline fraction
-and traffic ratio) and writes every leg's full result to --detail
-(gpurun_out/bench_detail.json), whose path the line gives.
+A plain run (`--gpus N --steps K --warmup W`) does what the headline needs and no more:
+it makes the main leg's batches resident, runs the W warmup and the K timed launches,
+writes the outputs when --dump-outputs is given and prints the line.  Everything else
+(the CPU baselines, the copy ceilings, every leg named above but the main one, the
+host-inclusive and receive-loop legs, config 1, the detail file) runs under --full, with
+the defaults of LEG_DEFAULTS; a leg asked for by its own option (--also, --tx, ...) runs
+without --full too.
+
+--dump-outputs DIR: after the timed launches, the buffers the last of them wrote (the
+records; the option records of --main-opts; config 4's flow events) as DIR/<name>.npy,
+see dump_outputs.  The batches are seeded, so the same arguments give the same files.
+
+Output: rank 0 prints ONE compact JSON line (< 8,000 bytes: the contract keys and the main
+leg's roofline; with --full its CPU baseline and per extra leg its kernel/step times,
+roofline fraction and traffic ratio) and, with --full, writes every leg's full result to
+the --detail file, whose path the line gives.
 """
 import argparse
 import ctypes
@@ -180,6 +192,29 @@ def algorithmic_bytes(hb, flow=False, rec_bytes=REC_BYTES):
     if flow:
         b += 16 * hb.n
     return b
+
+
+DUMP_BUDGET = 48 << 20    # bytes of .npy one --dump-outputs run writes, all ranks together
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: device buffers of fixed-size rows ({name: (uint8-viewable tensor, row
+    bytes)}: 80-B or 16-B records, 64-B option records, 8-B flow events) as
+    DIR/<name>.npy (<name>_rank<r>.npy at N > 1).  A row is written as its little-endian
+    32-bit words in float64, which holds every one exactly, so two builds compare word for
+    word.  When the buffers outgrow DUMP_BUDGET the same rows of each are kept: a seeded
+    choice without replacement, in ascending order, identical from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    row_out = sum(rb // 4 * 8 for _, rb in arrays.values())
+    keep = max(1, DUMP_BUDGET // world // row_out)
+    for name, (t, rb) in arrays.items():
+        a = t.contiguous().view(torch.uint8).cpu().numpy().reshape(-1, rb)
+        if a.shape[0] > keep:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))]
+        words = np.ascontiguousarray(a).view("<u4").astype(np.float64)
+        np.save(os.path.join(dirname, name + ("_rank%d" % rank if world > 1 else "") + ".npy"),
+                words)
 
 
 def time_parse(dbs, recs, flags, steps, warmup, world, flow=None, min_warm_s=0.3,
@@ -562,6 +597,14 @@ def run_config(cfg, args, rank, world, cpu=False, compact=False, opts=False, str
         cfg, hbs[0].n, len(hbs), flags))
     wall, kern_ms, warm = time_parse(dbs, recs, flags, args.steps, args.warmup, world, flow,
                                      args.min_warmup_s, compact, obufs)
+    if main and args.dump_outputs:
+        j = (args.steps - 1) % len(hbs)            # the batch of the last timed launch
+        arrays = {"records": (recs[j], rec_bytes)}
+        if opts:
+            arrays["opts"] = (obufs[j], 64)
+        if flow:
+            arrays["flow_events"] = (flow["ev"][j], 8)
+        dump_outputs(args.dump_outputs, arrays, rank, world)
 
     frames_step = sum(hb.n for hb in hbs) / len(hbs)
     bytes_step = sum(int(hb.lens().sum()) for hb in hbs) / len(hbs)
@@ -653,7 +696,7 @@ def run_config(cfg, args, rank, world, cpu=False, compact=False, opts=False, str
     # the records of batch 0 are read back before the copy references overwrite them
     g = as_records(recs[0].cpu().numpy()) if cpu and rank == 0 and not compact and not opts \
         else None
-    if cfg == 2 and main and not compact and not strong and world == 1:
+    if cfg == 2 and main and args.full and not compact and not strong and world == 1:
         try:
             out["copy_ceiling"] = copy_ceiling(dbs, recs, args.steps)
         except engine.RpktError as e:           # the development library is optional
@@ -1075,7 +1118,7 @@ def run_tx(cfg, mode, args, rank, world):
     achieved = alg / (kern_ms / 1e3) / 1e9
     traffic, tsrc = pmc_traffic_tx("%s%d" % (mode, cfg), hbs[0].n)   # the bench leg's name
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.tx_cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and args.tx_cpu_seconds > 0:
         # the leg's CPU restatement beside it: the oracle over the batch's first frames
         # (<= 64 MB), 1 thread, outputs allocated once outside the timed calls
         oracle, build = oracle_for_baseline()
@@ -1239,19 +1282,22 @@ def write_detail(path, main_res, extra, args, world, engine_build):
                   else str(o))
 
 
-# legs run by default at N = 1, and at N > 1 unless --all-legs (the N-rank job stays short:
-# the headline, config 4's sharded parse + counter reduce, and the strong-scaling legs)
+# legs run by default under --full at N = 1, and at N > 1 unless --all-legs (the N-rank job
+# stays short: the headline, config 4's sharded parse + counter reduce, and the
+# strong-scaling legs); without --full no leg runs by default
 LEG_DEFAULTS = {"also": ("3,4,5,7,10,11", "4"),
                 "tx": ("build2,build3,build11,forward2,forward10,opts5,optsc5,opts11,layers9,"
                        "fields9,tunnel13,encap13", ""),
                 "compact": ("2,3", ""), "strong": ("2,3", "2,3"), "opts": ("5", ""),
-                "ring": ("2,10", "")}
+                "ring": ("2,10", ""), "host": ("2,3", ""),
+                "rx_graph": ("16384x64,65536x16", "")}
 
 
 def resolve_legs(args, world):
     for k, (one, many) in LEG_DEFAULTS.items():
         if getattr(args, k) is None:
-            setattr(args, k, one if world == 1 or args.all_legs else many)
+            setattr(args, k, "" if not args.full else
+                    one if world == 1 or args.all_legs else many)
     return args
 
 
@@ -1297,12 +1343,13 @@ def main():
                     help="main leg as the fused parse + option walks (profiling it alone)")
     ap.add_argument("--compact", default=None,
                     help="configs also timed with 16-B compact records (extra.config<N>_compact)")
-    ap.add_argument("--host", default="2,3",
+    ap.add_argument("--host", default=None,
                     help="configs also timed host-inclusive at N=1 (pinned H2D frames -> parse "
-                         "-> D2H records, rpkt_amd.pipeline): extra.host_inclusive")
-    ap.add_argument("--rx-graph", default="16384x64,65536x16",
+                         "-> D2H records, rpkt_amd.pipeline): extra.host_inclusive (default 2,3)")
+    ap.add_argument("--rx-graph", default=None,
                     help="receive loops of small config-2 batches, FRAMESxSLOTS, timed eager "
-                         "and as a replayed hipGraph at N=1 (rpkt_amd.graphs): extra.rx_graph")
+                         "and as a replayed hipGraph at N=1 (rpkt_amd.graphs): extra.rx_graph "
+                         "(default 16384x64,65536x16)")
     ap.add_argument("--strong", default=None,
                     help="configs also timed as one batch split over the ranks "
                          "(extra.config<N>_strong)")
@@ -1317,6 +1364,12 @@ def main():
                     help="at N>1, run every N=1 default leg too (longer job)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="side file with every leg's full result (the stdout line names it)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines, the copy ceilings, the default "
+                         "extra legs (LEG_DEFAULTS), config 1 and the --detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed launch of the main leg left (its records; "
+                         "option records, flow events) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1355,7 +1408,7 @@ def main():
                                                                   args.gpus), file=sys.stderr)
             sys.exit(3)
     resolve_legs(args, world)
-    want_cpu = (not args.no_cpu) and world == 1
+    want_cpu = args.full and (not args.no_cpu) and world == 1
     if not args.cpu_threads:
         args.cpu_threads = usable_cpus()
 
@@ -1387,11 +1440,13 @@ def main():
 
     if rank == 0:
         build = engine.lib().rpkt_gpu_build_info().decode()
-        detail = os.path.relpath(args.detail, ROOT)
-        try:
-            write_detail(args.detail, main_res, extra, args, world, build)
-        except OSError as e:
-            detail = "not written: %s" % e
+        detail = None
+        if args.full:
+            detail = os.path.relpath(args.detail, ROOT)
+            try:
+                write_detail(args.detail, main_res, extra, args, world, build)
+            except OSError as e:
+                detail = "not written: %s" % e
         line = headline_line(main_res, extra, args, world, build, detail)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(line) + "\n").encode())

@@ -111,17 +111,22 @@ def test_headline_line_fits_the_driver_tail():
 
 
 def test_n_rank_default_leg_set():
-    """At N > 1 the default job is the headline, config 4 (shards + counter reduce) and the
-    strong legs; --all-legs restores the N = 1 set; explicit flags win."""
+    """Under --full, at N > 1 the default job is the headline, config 4 (shards + counter
+    reduce) and the strong legs; --all-legs restores the N = 1 set; explicit flags win.
+    Without --full no leg runs by default at any N, and explicit flags still win."""
     import argparse
     sys.path.insert(0, ROOT)
     import bench
 
     def ns(**kw):
         d = {k: None for k in bench.LEG_DEFAULTS}
-        d.update(all_legs=False)
+        d.update(all_legs=False, full=True)
         d.update(kw)
         return argparse.Namespace(**d)
+    for world in (1, 8):
+        plain = bench.resolve_legs(ns(full=False, all_legs=world == 8), world)
+        assert all(getattr(plain, k) == "" for k in bench.LEG_DEFAULTS), plain
+    assert bench.resolve_legs(ns(full=False, tx="layers9"), 1).tx == "layers9"
     a = bench.resolve_legs(ns(), 8)
     assert (a.also, a.tx, a.compact, a.strong, a.opts, a.ring) == ("4", "", "", "2,3", "", "")
     one = bench.resolve_legs(ns(), 1)
@@ -129,6 +134,40 @@ def test_n_rank_default_leg_set():
     allg = bench.resolve_legs(ns(all_legs=True), 8)
     assert allg.tx == one.tx and allg.also == one.also
     assert bench.resolve_legs(ns(tx="layers9"), 8).tx == "layers9"
+
+
+def test_dump_outputs_words_exact_and_sample_fixed(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): every row as its little-endian 32-bit words in
+    float64, exactly; a buffer past the budget is cut to the same ascending rows of every
+    array on every call; N > 1 ranks write their own files."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(11)
+    n = 1000
+    recs = rng.integers(0, 256, n * 80, dtype=np.uint8)
+    recs[:4] = 0xff                                    # a word of 2^32 - 1
+    ev = rng.integers(-2**63, 2**63 - 1, n, dtype=np.int64)
+    arrays = {"records": (torch.from_numpy(recs), 80), "flow_events": (torch.from_numpy(ev), 8)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, 0, 1)
+    got = np.load(tmp_path / "a" / "records.npy")
+    assert got.dtype == np.float64 and got.shape == (n, 20) and got[0, 0] == 2.0**32 - 1
+    assert got.astype("<u4").tobytes() == recs.tobytes()
+    assert np.load(tmp_path / "a" / "flow_events.npy").astype("<u4").tobytes() == ev.tobytes()
+    # 100 rows of (20 + 2) float64 words fit the budget: the same 100 rows of both arrays
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 100 * 22 * 8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays, 0, 1)
+    cut = np.load(tmp_path / "b" / "records.npy")
+    assert cut.shape == (100, 20) and np.array_equal(cut, np.load(tmp_path / "c" / "records.npy"))
+    rows = [int(np.flatnonzero((got == r).all(axis=1))[0]) for r in cut]
+    assert rows == sorted(set(rows))
+    assert np.array_equal(np.load(tmp_path / "b" / "flow_events.npy"),
+                          np.load(tmp_path / "a" / "flow_events.npy")[rows])
+    bench.dump_outputs(str(tmp_path / "r"), arrays, 1, 2)
+    assert np.load(tmp_path / "r" / "records_rank1.npy").shape == (50, 20)
+    assert sorted(os.listdir(tmp_path / "r")) == ["flow_events_rank1.npy", "records_rank1.npy"]
 
 
 @pytest.mark.parametrize("threads", [1, 3])

@@ -74,7 +74,7 @@ def test_ranks_hip_flow_counters_equal_whole_batch(tmp_path, world):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_launches_n_ranks(tmp_path, world):
-    """bench.py --gpus N starts its own N ranks (no torchrun) and runs the N-rank default
+    """bench.py --gpus N --full starts its own N ranks (no torchrun) and runs the N-rank default
     leg set (the headline, config 4's shards + counter reduce, the strong legs): the
     counter sum covers every frame of every launch of every rank and is verified against
     torch's sum, and rank 0's one stdout line parses and fits the driver's 8,000-char
@@ -83,7 +83,7 @@ def test_bench_launches_n_ranks(tmp_path, world):
     env.pop("WORLD_SIZE", None)
     detail = str(tmp_path / "detail.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world),
-                        "--dist-backend", "gloo", "--no-cpu", "--frames", "200000", "--steps",
+                        "--full", "--dist-backend", "gloo", "--no-cpu", "--frames", "200000", "--steps",
                         "3", "--warmup", "1", "--min-warmup-s", "0", "--detail", detail],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -286,7 +286,7 @@ def test_bench_nccl_ranks_sharing_one_gpu(tmp_path, comm):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--share-gpu", "--reduce-comm", comm, "--no-cpu", "--frames", "200000",
+                        "--full", "--share-gpu", "--reduce-comm", comm, "--no-cpu", "--frames", "200000",
                         "--steps", "3", "--warmup", "1", "--min-warmup-s", "0", "--detail",
                         str(tmp_path / "d.json")], capture_output=True, text=True, timeout=300,
                        env=env, cwd=ROOT)
@@ -323,7 +323,7 @@ def test_bench_under_torchrun_as_the_driver_launches_it(tmp_path):
     s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu",
+                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--share-gpu",
                         "--no-cpu", "--frames", "200000", "--steps", "3", "--warmup", "1",
                         "--min-warmup-s", "0", "--detail", str(tmp_path / "d.json")],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)

@@ -1,4 +1,4 @@
-"""Regenerate DESIGN.md §6's roofline table from a bench detail file (bench.py --detail,
+"""Regenerate DESIGN.md §6's roofline table from a bench detail file (bench.py --full --detail,
 every leg's full result) and the committed PMC traffic summaries
 (profiles/traffic_*.json).  Host side.
 
