@@ -363,6 +363,13 @@ extern "C" {
     /// launch.
     pub fn rpkt_gpu_parse_tunnel_ring(slots: *const rpkt_tun_ring_slot_t, n_slots: u32,
                                       flags: u32, n_buckets: u32, stream: *mut c_void) -> c_int;
+    /// rpkt_gpu_parse_tunnel_batch's three records per mbuf chain, under the Pbuf rules
+    /// (header sizes against chunk(), totals against remaining()).
+    pub fn rpkt_gpu_parse_tunnel_chains(chains: *const rpkt_chains_t, flags: u32,
+                                        outer_dev: *mut rpkt_rec_t, tun_dev: *mut rpkt_tun_t,
+                                        inner_dev: *mut rpkt_rec_t,
+                                        flow_ev_dev: *mut rpkt_flow_ev_t, n_buckets: u32,
+                                        stream: *mut c_void) -> c_int;
     pub fn rpkt_gpu_build_tunnel_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
                                        tun_dev: *const rpkt_tun_t, flags: u32, built_dev: *mut u8,
                                        stream: *mut c_void) -> c_int;

@@ -397,3 +397,17 @@ pub unsafe fn parse_options_batch(batch: &ffi::rpkt_batch_t, flags: u32, recs_de
     check(ffi::rpkt_gpu_parse_options_batch(batch, flags, recs_dev, opts_dev,
                                             core::ptr::null_mut(), 0, stream))
 }
+
+/// rpkt_gpu_parse_tunnel_chains: the outer record, the tunnel and the inner record of every
+/// mbuf chain (tunnels over rpkt-dpdk's Pbuf), without flow events.
+///
+/// # Safety
+/// `chains` must describe device memory valid for the call; `outer_dev` and `inner_dev` must
+/// hold `chains.n_chains` records and `tun_dev` as many rpkt_tun_t (all 16-byte aligned) on
+/// the same device.
+pub unsafe fn parse_tunnel_chains(chains: &ffi::rpkt_chains_t, flags: u32, outer_dev: *mut Rec,
+                                  tun_dev: *mut ffi::rpkt_tun_t, inner_dev: *mut Rec,
+                                  stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_parse_tunnel_chains(chains, flags, outer_dev, tun_dev, inner_dev,
+                                            core::ptr::null_mut(), 0, stream))
+}

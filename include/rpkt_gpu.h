@@ -499,6 +499,45 @@ typedef struct rpkt_tun_ring_slot {
 int rpkt_gpu_parse_tunnel_ring(const rpkt_tun_ring_slot_t* slots, uint32_t n_slots,
                                uint32_t flags, uint32_t n_buckets, void* stream);
 
+/* Tunnels over mbuf chains: rpkt_gpu_parse_tunnel_batch's three records per chain, with
+ * every view's tests taken as they are over a Pbuf (rpkt-dpdk/src/pbuf.rs:49-104; the same
+ * Vxlan::parse(udp.payload()) chain of rpkt/tests/vlan_mpls_tests.rs:237-251 runs
+ * unchanged over one) -- jumbo overlay traffic in 2048-B mbuf data rooms without
+ * flattening it on the host first:
+ *   outer_dev[p]  byte for byte the record rpkt_gpu_parse_chains writes for chain p with
+ *                 the same flags;
+ *   tun_dev[p]    the tunnel of the Pbuf the outer view's payload() returned, dispatched as
+ *                 rpkt_gpu_parse_tunnel_batch dispatches.  Header sizes are tested against
+ *                 chunk() (the rest of the segment holding the header's first byte, cut at
+ *                 the current packet end, empty segments skipped as advance_common walks
+ *                 them), total lengths against remaining(): Vxlan::parse chunk >= 8
+ *                 (vxlan/generated.rs:32-39); Gtpv1::parse chunk >= 8 and header_len <=
+ *                 chunk, packet_len <= remaining (gtpv1/generated.rs:33-49); each GTP-U
+ *                 extension header against its own chunk (:336-341, :461-466, :587-592,
+ *                 :747-752, :880-892, the NrUp / PduSessionUp group parses); Gre::parse
+ *                 header_len in [4, chunk]; GreForPPTP::parse chunk >= 8 and header_len <=
+ *                 chunk, payload_len + header_len <= remaining (gre/generated.rs:371-386).
+ *                 A tunnel or extension header that straddles a segment boundary is
+ *                 therefore RPKT_T_BAD / RPKT_T_EXT_BAD, as the reference returns Err: it
+ *                 is not reassembled.  tun_off / inner_off are logical positions in the
+ *                 chain's bytes;
+ *   inner_dev[p]  the record of the sub-chain [inner_off, the tunnel payload's end) under
+ *                 the same Pbuf rules (an inner IPv4 / IPv6 packet parsed from its IP
+ *                 header: ethertype = inner_type, n_vlan 0, MACs 0), l3_off / l4_off /
+ *                 payload_off / ip6_pdst_off logical positions in the OUTER chain,
+ *                 frame_len = the inner frame's length, l4_sum = from_buf over the
+ *                 segments with the odd-byte pairing of rpkt/src/checksum.rs:77-111;
+ *                 status RPKT_S_NO_INNER (all else 0) when tun_dev[p].status != RPKT_T_OK.
+ * flags and flow_ev_dev / n_buckets as rpkt_gpu_parse_tunnel_batch (the event is the inner
+ * record's when the tunnel decoded, else the outer's); chains as rpkt_gpu_parse_chains.
+ * Record offsets are 16-bit: a chain longer than 65,535 B has them truncated, as
+ * rpkt_gpu_parse_chains truncates them, and the tunnel is then looked for at the truncated
+ * position.  outer_dev / inner_dev n_chains * 80 B, tun_dev n_chains * 16 B, all 16-byte
+ * aligned. */
+int rpkt_gpu_parse_tunnel_chains(const rpkt_chains_t* chains, uint32_t flags,
+                                 rpkt_rec_t* outer_dev, rpkt_tun_t* tun_dev, rpkt_rec_t* inner_dev,
+                                 rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream);
+
 /* ---- TX side ---------------------------------------------------------------- */
 
 /* Build flags: fill a checksum the way the NIC TX offload requested by the

@@ -67,7 +67,7 @@ EXPORTS = ["rpkt_gpu_abi_version", "rpkt_gpu_build_info", "rpkt_gpu_status_name"
            "rpkt_gpu_parse_ring", "rpkt_gpu_parse_ring_compact", "rpkt_gpu_coll_unique_id",
            "rpkt_gpu_comm_init", "rpkt_gpu_comm_destroy", "rpkt_gpu_comm_init_timeout",
            "rpkt_gpu_comm_abort", "rpkt_gpu_parse_tunnel_batch", "rpkt_gpu_build_tunnel_batch",
-           "rpkt_gpu_parse_tunnel_ring"]
+           "rpkt_gpu_parse_tunnel_ring", "rpkt_gpu_parse_tunnel_chains"]
 COLL_ID_BYTES = 128
 
 _lib = None
@@ -148,6 +148,11 @@ def lib():
         L.rpkt_gpu_parse_tunnel_ring.argtypes = [ctypes.POINTER(TunRingSlot), ctypes.c_uint32,
                                                  ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
         L.rpkt_gpu_parse_tunnel_ring.restype = ctypes.c_int
+        L.rpkt_gpu_parse_tunnel_chains.argtypes = [ctypes.POINTER(Chains), ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint32, ctypes.c_void_p]
+        L.rpkt_gpu_parse_tunnel_chains.restype = ctypes.c_int
         L.rpkt_gpu_build_tunnel_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.c_void_p, ctypes.c_void_p]
@@ -545,6 +550,27 @@ def parse_chains(chains, flags=3, recs=None, flow_ev=None, n_buckets=0, stream=N
                                      n_buckets, _stream_ptr(stream))
     _check(rc, "rpkt_gpu_parse_chains")
     return (recs, flow_ev) if flags & F_FLOW_EV else recs
+
+
+def parse_tunnel_chains(chains, flags=3, outer=None, tun=None, inner=None, stream=None,
+                        flow_ev=None, n_buckets=0):
+    """rpkt_gpu_parse_tunnel_chains: parse_tunnel_batch over mbuf chains.  Returns (outer
+    records, rpkt_tun_t, inner records) as uint8 tensors (n * 80, n * 16, n * 80 bytes);
+    with RPKT_F_FLOW_EV also the flow events (int64 tensor of n)."""
+    torch = _torch()
+    dev = chains.buf.device
+    outer = alloc_records(chains.n, dev) if outer is None else outer
+    inner = alloc_records(chains.n, dev) if inner is None else inner
+    tun = torch.empty(chains.n * 16, dtype=torch.uint8, device=dev) if tun is None else tun
+    if flags & F_FLOW_EV and flow_ev is None:
+        flow_ev = torch.empty(chains.n, dtype=torch.int64, device=dev)
+    d = chains.desc()
+    rc = lib().rpkt_gpu_parse_tunnel_chains(ctypes.byref(d), flags, outer.data_ptr(),
+                                            tun.data_ptr(), inner.data_ptr(),
+                                            flow_ev.data_ptr() if flow_ev is not None else None,
+                                            n_buckets, _stream_ptr(stream))
+    _check(rc, "rpkt_gpu_parse_tunnel_chains")
+    return (outer, tun, inner, flow_ev) if flags & F_FLOW_EV else (outer, tun, inner)
 
 
 def build_batch(batch, recs, flags=3, built=None, stream=None):

@@ -15,7 +15,8 @@ and a config 13 / 14 batch), the layer walk; (b) a generator batch of a random c
 build with random checksum flags over its (IPv4 and IPv6) records, the forward with and
 without RPKT_F_IPV6, and the encapsulation build over a tunnel batch (configs 13 / 14); (c)
 a fuzzed mbuf-chain batch (configs 8 / 12) through the chain
-parse.  Build and forward rewrite frames in place, so they run on generator batches
+parse, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
+random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py.  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -35,6 +36,7 @@ from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_recor
                               as_records16, as_tunnels, project16)
 
 import fuzz_layouts  # noqa: E402
+import tunnel_chain_model  # noqa: E402
 import tunnel_frames  # noqa: E402
 from test_gpu_parity import assert_same, assert_same16  # noqa: E402
 
@@ -191,6 +193,28 @@ def check_chains(rng, seed):
     return {"cfg": cfg, "n": int(hc.n), "flags": flags}
 
 
+def check_tunnel_chains(rng, seed):
+    """rpkt_gpu_parse_tunnel_chains (records and flow events) against the model."""
+    if rng.random() < 0.7:
+        hc = gen.make_chains(14, n=int(rng.integers(1, 6000)), layout="fuzz", seed=seed)
+    else:
+        frames = tunnel_frames.odd_frames(seed=seed, n=int(rng.integers(1, 300)))
+        lens = [tunnel_chain_model.cut_at(len(f), rng.integers(0, len(f) + 1, int(rng.integers(0, 6))))
+                for f in frames]
+        hc = tunnel_chain_model.lay_out(frames, lens, gap=int(rng.integers(0, 40)))
+    flags = int(rng.integers(0, 4)) | (F_IPV6 if rng.random() < 0.6 else 0)
+    nb = int(rng.integers(1, 3000))
+    dc = engine.DeviceChains.from_host(hc)
+    go, gt, gi, gev = engine.parse_tunnel_chains(dc, flags | F_FLOW_EV, n_buckets=nb)
+    wo, wt, wi = tunnel_chain_model.tunnel_chains(hc.buf, hc.segs, hc.chain_first, flags)
+    assert_same(as_records(go.cpu().numpy()), wo)
+    assert as_tunnels(gt.cpu().numpy()).tobytes() == wt.tobytes(), "chain tunnel records"
+    assert_same(as_records(gi.cpu().numpy()), wi)
+    assert np.array_equal(gev.cpu().numpy().view(np.uint64),
+                          oracle.tunnel_flow_events(wo, wt, wi, nb)), "chain tunnel flow events"
+    return {"n": int(hc.n), "flags": flags}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=8.0)
@@ -215,6 +239,8 @@ def main():
                 rec["encap"] = check_encap(rng, seed)
                 step = "chains"
                 rec["chains"] = check_chains(rng, seed)
+                step = "tunnel_chains"
+                rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")
