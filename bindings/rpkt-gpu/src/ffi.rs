@@ -370,6 +370,14 @@ extern "C" {
                                         inner_dev: *mut rpkt_rec_t,
                                         flow_ev_dev: *mut rpkt_flow_ev_t, n_buckets: u32,
                                         stream: *mut c_void) -> c_int;
+    /// The next tunnel level of `batch` from the level before's records (nested tunnels);
+    /// every offset written is a position in the outermost frame.
+    pub fn rpkt_gpu_parse_tunnel_next(batch: *const rpkt_batch_t, flags: u32,
+                                      tun_dev: *const rpkt_tun_t, inner_dev: *const rpkt_rec_t,
+                                      tun_next_dev: *mut rpkt_tun_t,
+                                      inner_next_dev: *mut rpkt_rec_t,
+                                      flow_ev_dev: *mut rpkt_flow_ev_t, n_buckets: u32,
+                                      stream: *mut c_void) -> c_int;
     pub fn rpkt_gpu_build_tunnel_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
                                        tun_dev: *const rpkt_tun_t, flags: u32, built_dev: *mut u8,
                                        stream: *mut c_void) -> c_int;

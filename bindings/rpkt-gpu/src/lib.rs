@@ -411,3 +411,19 @@ pub unsafe fn parse_tunnel_chains(chains: &ffi::rpkt_chains_t, flags: u32, outer
     check(ffi::rpkt_gpu_parse_tunnel_chains(chains, flags, outer_dev, tun_dev, inner_dev,
                                             core::ptr::null_mut(), 0, stream))
 }
+
+/// rpkt_gpu_parse_tunnel_next: the next tunnel level (nested tunnels) from the tunnel and
+/// inner records of the level before, without flow events.
+///
+/// # Safety
+/// `batch` must describe device memory valid for the call; `tun_dev` / `inner_dev` must be the
+/// records an earlier tunnel parse wrote for this same batch; `tun_next_dev` must hold
+/// `batch.n` rpkt_tun_t and `inner_next_dev` as many records (all 16-byte aligned, none
+/// aliasing an input) on the same device.
+pub unsafe fn parse_tunnel_next(batch: &ffi::rpkt_batch_t, flags: u32,
+                                tun_dev: *const ffi::rpkt_tun_t, inner_dev: *const Rec,
+                                tun_next_dev: *mut ffi::rpkt_tun_t, inner_next_dev: *mut Rec,
+                                stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_parse_tunnel_next(batch, flags, tun_dev, inner_dev, tun_next_dev,
+                                          inner_next_dev, core::ptr::null_mut(), 0, stream))
+}

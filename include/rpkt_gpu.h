@@ -538,6 +538,47 @@ int rpkt_gpu_parse_tunnel_chains(const rpkt_chains_t* chains, uint32_t flags,
                                  rpkt_rec_t* outer_dev, rpkt_tun_t* tun_dev, rpkt_rec_t* inner_dev,
                                  rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream);
 
+/* Nested tunnels: the next tunnel level of a batch, from the records of the level before
+ * (a UPF's GTP-U over a VXLAN underlay, VXLAN over GRE, GRE inside GTP-U).  The reference
+ * has no depth limit: a receive loop keeps chaining the views, Vxlan::parse(udp.payload())
+ * -> EtherFrame::parse -> ... -> Gtpv1::parse(udp.payload()) -> Ipv4::parse, because every
+ * view takes any Buf.  Here each level is one call, and the call can be applied to its own
+ * output for a third level and beyond.
+ *   tun_dev / inner_dev   what rpkt_gpu_parse_tunnel_batch wrote for this SAME batch (level
+ *                 1), or what an earlier call of this entry wrote for it (level k);
+ *   tun_next_dev[i] / inner_next_dev[i]   level k + 1, in the same formats.  Where
+ *                 tun_dev[i].status != RPKT_T_OK: kind NONE / status RPKT_T_NONE (all else
+ *                 0) and status RPKT_S_NO_INNER (all else 0).  Otherwise the level-k inner
+ *                 frame is bytes [inner_off, inner_off + inner_dev[i].frame_len) of frame i
+ *                 and inner_dev[i] plays the outer record's part: the tunnel is dispatched
+ *                 from it and decoded exactly as rpkt_gpu_parse_tunnel_batch dispatches and
+ *                 decodes from its outer record (the same rpkt_tun_status values), and the
+ *                 next inner frame is parsed and verified as that entry's inner frame is
+ *                 (an inner IP packet from its IP header: ethertype = inner_type, n_vlan 0,
+ *                 MACs 0; frame_len = the innermost frame's length).
+ * Every offset written -- tun_off, inner_off, the record's l3_off / l4_off / payload_off /
+ * ip6_pdst_off -- is a position in the OUTERMOST frame, as the level-1 offsets are.  The
+ * sums of the levels before are in their records; this pass computes the innermost
+ * record's sums only.
+ * flags: RPKT_F_IP_SUM, RPKT_F_L4_SUM, RPKT_F_IPV6 (any other bit: RPKT_E_INVAL) and
+ * RPKT_F_FLOW_EV: flow_ev_dev[i] (n * 8 B, 8-byte aligned; n_buckets 1..
+ * RPKT_FLOW_MAX_BUCKETS) is written ONLY where tun_next_dev[i].status == RPKT_T_OK, with
+ * the event of inner_next_dev[i] as rpkt_gpu_parse_tunnel_batch forms an inner record's;
+ * the other entries are left as they are, so passing the level-1 call's event buffer moves
+ * the accounting to the innermost flow and changes nothing else.
+ * Flat batches (packed or strided); n == 0 returns RPKT_OK.  tun_next_dev == tun_dev or
+ * inner_next_dev == inner_dev is RPKT_E_INVAL; tun_dev / inner_dev are not written.
+ * The records must come from a call on the same batch.  With other records the outputs are
+ * unspecified, but every frame byte is still read through the bounds-checked buffer
+ * resource, with [inner_off, + frame_len) clamped to frame i's span: wrong records, never a
+ * fault.  Frames longer than 65,535 B have truncated offsets, as everywhere else.
+ * inner_dev / inner_next_dev n * 80 B, tun_dev / tun_next_dev n * 16 B, all 16-byte
+ * aligned. */
+int rpkt_gpu_parse_tunnel_next(const rpkt_batch_t* batch, uint32_t flags,
+                               const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                               rpkt_tun_t* tun_next_dev, rpkt_rec_t* inner_next_dev,
+                               rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream);
+
 /* ---- TX side ---------------------------------------------------------------- */
 
 /* Build flags: fill a checksum the way the NIC TX offload requested by the

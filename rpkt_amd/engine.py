@@ -67,7 +67,8 @@ EXPORTS = ["rpkt_gpu_abi_version", "rpkt_gpu_build_info", "rpkt_gpu_status_name"
            "rpkt_gpu_parse_ring", "rpkt_gpu_parse_ring_compact", "rpkt_gpu_coll_unique_id",
            "rpkt_gpu_comm_init", "rpkt_gpu_comm_destroy", "rpkt_gpu_comm_init_timeout",
            "rpkt_gpu_comm_abort", "rpkt_gpu_parse_tunnel_batch", "rpkt_gpu_build_tunnel_batch",
-           "rpkt_gpu_parse_tunnel_ring", "rpkt_gpu_parse_tunnel_chains"]
+           "rpkt_gpu_parse_tunnel_ring", "rpkt_gpu_parse_tunnel_chains",
+           "rpkt_gpu_parse_tunnel_next"]
 COLL_ID_BYTES = 128
 
 _lib = None
@@ -153,6 +154,12 @@ def lib():
                                                    ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_uint32, ctypes.c_void_p]
         L.rpkt_gpu_parse_tunnel_chains.restype = ctypes.c_int
+        L.rpkt_gpu_parse_tunnel_next.argtypes = [ctypes.POINTER(Batch), ctypes.c_uint32,
+                                                 ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.c_void_p]
+        L.rpkt_gpu_parse_tunnel_next.restype = ctypes.c_int
         L.rpkt_gpu_build_tunnel_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.c_void_p, ctypes.c_void_p]
@@ -300,6 +307,54 @@ def parse_tunnel_batch(batch, flags=3, outer=None, tun=None, inner=None, stream=
                                            n_buckets, _stream_ptr(stream))
     _check(rc, "rpkt_gpu_parse_tunnel_batch")
     return (outer, tun, inner, flow_ev) if flags & F_FLOW_EV else (outer, tun, inner)
+
+
+def parse_tunnel_next(batch, tun, inner, flags=3, tun_next=None, inner_next=None, flow_ev=None,
+                      n_buckets=0, stream=None):
+    """rpkt_gpu_parse_tunnel_next: the next tunnel level of `batch` from the level before
+    (`tun`, `inner`: parse_tunnel_batch's on this batch, or an earlier call's of this
+    function).  Returns (tun_next, inner_next), uint8 tensors of n * 16 and n * 80 bytes, every
+    offset a position in the outermost frame.  With RPKT_F_FLOW_EV, flow_ev (required: the
+    level before's events) gets the innermost record's event where the next tunnel decoded
+    and keeps its other entries."""
+    torch = _torch()
+    dev = batch.frames.device
+    if tun_next is None:
+        tun_next = torch.empty(batch.n * 16, dtype=torch.uint8, device=dev)
+    inner_next = alloc_records(batch.n, dev) if inner_next is None else inner_next
+    d = batch.desc()
+    rc = lib().rpkt_gpu_parse_tunnel_next(ctypes.byref(d), flags, tun.data_ptr(),
+                                          inner.data_ptr(), tun_next.data_ptr(),
+                                          inner_next.data_ptr(),
+                                          flow_ev.data_ptr() if flow_ev is not None else None,
+                                          n_buckets, _stream_ptr(stream))
+    _check(rc, "rpkt_gpu_parse_tunnel_next")
+    return tun_next, inner_next
+
+
+def parse_tunnel_levels(batch, flags=3, depth=2, n_buckets=0, stream=None, buffers=None):
+    """`depth` tunnel levels of a batch on one stream: parse_tunnel_batch, then depth - 1
+    parse_tunnel_next passes, each on the level before.  Returns (outer, levels), or with
+    RPKT_F_FLOW_EV (outer, levels, flow_ev), where levels[k] is level k + 1's (tun, inner)
+    and flow_ev holds each frame's innermost decoded flow.  `buffers`: two (tun, inner) tensor
+    pairs to ping-pong between when only the last level is wanted (levels then holds the last
+    two levels written; earlier ones are overwritten); by default every level gets its own
+    tensors."""
+    if depth < 1:
+        raise RpktError("parse_tunnel_levels: depth %d" % depth)
+    if buffers is not None and len(buffers) != 2:
+        raise RpktError("parse_tunnel_levels: buffers takes two (tun, inner) pairs")
+    t0, i0 = buffers[0] if buffers is not None else (None, None)
+    res = parse_tunnel_batch(batch, flags, tun=t0, inner=i0, stream=stream, n_buckets=n_buckets)
+    outer, ev = res[0], (res[3] if flags & F_FLOW_EV else None)
+    levels = [(res[1], res[2])]
+    for k in range(1, depth):
+        tn, inn = buffers[k % 2] if buffers is not None else (None, None)
+        levels.append(parse_tunnel_next(batch, levels[-1][0], levels[-1][1], flags, tn, inn,
+                                        ev, n_buckets, stream))
+    if buffers is not None:
+        levels = levels[-2:]
+    return (outer, levels, ev) if flags & F_FLOW_EV else (outer, levels)
 
 
 def tunnel_ring_slots(batches, outers, tuns, inners, flow_evs=None):

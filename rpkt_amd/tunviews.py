@@ -17,6 +17,9 @@ The reference views and the chains its tests walk:
             Dl/UlPduSessionInfo: :319-1517) walk to the T-PDU as gtpv1_test.rs:199-231,
             284-320, 468-505 do; `Gtpv1.t_pdu()` jumps there directly
   Gre       rpkt/src/gre/generated.rs:17-110, 222-280 (checksum, offset, key, sequence)
+Nested tunnels (rpkt_gpu_parse_tunnel_next) read on through the same views: give
+TunnelPacket the deeper levels' (tun, inner) records and each tunnel view's payload() cursor
+carries the next level, all cursors positions in the outermost frame.
 Ok / Err follow the engine's decode (rpkt_tun_t.kind / status): `parse` is Ok exactly
 where the reference parse returned Ok for this frame.  Getters come from the tunnel
 record; the few the record does not carry (GTP packet_len / npdu / next extension, GRE
@@ -31,10 +34,10 @@ from .views import Cursor, Err, EtherType, Ok
 class _TunRec:
     """The outer record as the outer views see it, carrying its tunnel and inner records
     (so the payload cursor a Udp / Ipv4 view returns still knows them)."""
-    __slots__ = ("rec", "tun", "inner")
+    __slots__ = ("rec", "tun", "inner", "deeper")
 
-    def __init__(self, rec, tun, inner):
-        self.rec, self.tun, self.inner = rec, tun, inner
+    def __init__(self, rec, tun, inner, deeper=()):
+        self.rec, self.tun, self.inner, self.deeper = rec, tun, inner, tuple(deeper)
 
     def __getitem__(self, k):
         return self.rec[k]
@@ -43,10 +46,27 @@ class _TunRec:
         return np.asarray(self.rec)
 
 
-def TunnelPacket(outer, tun, inner, frame=None):
+def _inner_stage(t):
+    return "ether" if int(t["inner_type"]) == EtherType.TRANS_ETH_BRIDGE or \
+        int(t["kind"]) == TUN_KIND["VXLAN"] else "l3"
+
+
+def TunnelPacket(outer, tun, inner, frame=None, deeper=(), parent=None):
     """Cursor::new(frame) over a frame rpkt_gpu_parse_tunnel_batch parsed: the outer chain
-    starts here; the tunnel views take their cursors from its payloads."""
-    return Cursor(_TunRec(outer, tun, inner), frame, "ether", 0, 0, int(outer["frame_len"]))
+    starts here; the tunnel views take their cursors from its payloads.
+
+    Nested tunnels (rpkt_gpu_parse_tunnel_next): `deeper` lists the (tun, inner) records of
+    the levels after this one, so each tunnel view's payload() cursor carries the next
+    level and the chain reads on, Vxlan.parse(udp.payload()) -> EtherFrame.parse ->
+    ... -> Gtpv1.parse(udp.payload()), as the reference chains its views over any Buf.  To
+    start a chain at level k's inner frame instead, TunnelPacket(inner_k, tun_next,
+    inner_next, frame, parent=tun_k): `parent` places the cursor at that frame's first
+    header (its position in the outermost frame; an IP packet starts at "l3")."""
+    rec = _TunRec(outer, tun, inner, deeper)
+    if parent is None:
+        return Cursor(rec, frame, "ether", 0, 0, int(outer["frame_len"]))
+    return Cursor(rec, frame, _inner_stage(parent), 0, int(parent["inner_off"]),
+                  int(outer["frame_len"]))
 
 
 def _tun(buf):
@@ -64,9 +84,10 @@ def _inner_cursor(buf, t):
             if int(t["kind"]) != TUN_KIND["GRE"] else int(buf.rec["l3_off"]) + \
             int(buf.rec["ip_packet_len"])
         return Cursor(buf.rec, buf.frame, "raw", 0, off, max(0, end - off))
-    stage = "ether" if int(t["inner_type"]) == EtherType.TRANS_ETH_BRIDGE or \
-        int(t["kind"]) == TUN_KIND["VXLAN"] else "l3"
-    return Cursor(inner, buf.frame, stage, 0, off, n)
+    deeper = buf.rec.deeper
+    if deeper:                                     # the next level's records travel along
+        inner = _TunRec(inner, deeper[0][0], deeper[0][1], deeper[1:])
+    return Cursor(inner, buf.frame, _inner_stage(t), 0, off, n)
 
 
 def _frame_bytes(buf, off, n):

@@ -16,7 +16,10 @@ build with random checksum flags over its (IPv4 and IPv6) records, the forward w
 without RPKT_F_IPV6, and the encapsulation build over a tunnel batch (configs 13 / 14); (c)
 a fuzzed mbuf-chain batch (configs 8 / 12) through the chain
 parse, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
-random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py.  Build and forward rewrite frames in place, so they run on generator batches
+random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py; (d)
+a nested tunnel batch (tests/nested_tunnel_ref.py's recipe: config 13 / 14 frames, frame k
+wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level passes
+(rpkt_gpu_parse_tunnel_next, records and flow events) against the oracle composition.  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -36,6 +39,7 @@ from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_recor
                               as_records16, as_tunnels, project16)
 
 import fuzz_layouts  # noqa: E402
+import nested_tunnel_ref  # noqa: E402
 import tunnel_chain_model  # noqa: E402
 import tunnel_frames  # noqa: E402
 from test_gpu_parity import assert_same, assert_same16  # noqa: E402
@@ -215,6 +219,29 @@ def check_tunnel_chains(rng, seed):
     return {"n": int(hc.n), "flags": flags}
 
 
+def check_tunnel_next(rng, seed):
+    """rpkt_gpu_parse_tunnel_next over the nested recipe: levels 2 and 3 (records, and the
+    flow events handed on from level 1) against the oracle composition."""
+    cfg = int(rng.choice([13, 14]))
+    hb = nested_tunnel_ref.nested_frames(cfg, int(rng.integers(1, 3000 if cfg == 14 else 400)), seed,
+                                         lead=int(rng.integers(0, 16)))
+    flags = int(rng.integers(0, 4)) | (F_IPV6 if rng.random() < 0.7 else 0)
+    nb = int(rng.integers(1, 3000))
+    db = engine.DeviceBatch.from_host(hb)
+    go, gt, gi, gev = engine.parse_tunnel_batch(db, flags | F_FLOW_EV, n_buckets=nb)
+    t, i = as_tunnels(gt.cpu().numpy()), as_records(gi.cpu().numpy())
+    want_ev = gev.cpu().numpy().view(np.uint64).copy()
+    for level in (2, 3):
+        gt, gi = engine.parse_tunnel_next(db, gt, gi, flags | F_FLOW_EV, flow_ev=gev, n_buckets=nb)
+        wt, wi, sub = nested_tunnel_ref.next_level(hb, flags, t, i, with_sub=True)
+        want_ev = nested_tunnel_ref.expected_events(want_ev, sub, nb)
+        assert as_tunnels(gt.cpu().numpy()).tobytes() == wt.tobytes(), "level %d tunnel records" % level
+        assert_same(as_records(gi.cpu().numpy()), wi)
+        assert np.array_equal(gev.cpu().numpy().view(np.uint64), want_ev), "level %d flow events" % level
+        t, i = wt, wi
+    return {"cfg": cfg, "n": int(hb.n), "flags": flags}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=8.0)
@@ -241,6 +268,8 @@ def main():
                 rec["chains"] = check_chains(rng, seed)
                 step = "tunnel_chains"
                 rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
+                step = "tunnel_next"
+                rec["tunnel_next"] = check_tunnel_next(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")
