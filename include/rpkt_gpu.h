@@ -83,7 +83,35 @@ enum rpkt_status {
  * header at an extension type -> RPKT_S_L4_OTHER (as a third VLAN tag -> NOT_IPV4). */
 #define RPKT_MAX_IP6_EXT 8
 
-/* ---- API return codes ---- */
+/* ---- API return codes ----
+ * Every entry checks its arguments before it launches anything and returns the status of
+ * the first check that fails.  The order (one set of checks, rpkt_amd/csrc/rpkt_args.h;
+ * pinned case by case by tests/test_abi_status_matrix.py):
+ *   batch entries (parse, compact, options, build, forward, layers): a NULL descriptor or
+ *     required output (E_INVAL); unknown flags (E_INVAL); n == 0 (RPKT_OK, nothing else is
+ *     looked at); NULL frames_dev (E_INVAL; forward: or n_forbid without forbid_dev);
+ *     frames_bytes (E_TOO_LARGE); no layout -- offsets_dev NULL and stride 0 (E_INVAL);
+ *     alignment (E_ALIGN); with RPKT_F_FLOW_EV a NULL flow_ev_dev or n_buckets outside
+ *     1..RPKT_FLOW_MAX_BUCKETS (E_INVAL), then flow_ev_dev's alignment (E_ALIGN);
+ *   chain entries: the same with, in the batch's place, NULL chain_first_dev / buf_dev /
+ *     segs_dev (E_INVAL), then buf_bytes and n_segs (E_TOO_LARGE); segs_dev's alignment goes
+ *     with the other alignments;
+ *   tunnel entries (batch, chains, next, ring): only the descriptor is tested before the
+ *     flags and n == 0, the record pointers after it with frames_dev;
+ *   ring entries: NULL slots with n_slots > 0, the flags, then each non-empty slot in
+ *     order with its batch entry's checks, all before the first launch.
+ * Where an entry leaves that order (kept as it is, callers may rely on it):
+ *   rpkt_gpu_parse_tunnel_batch and each slot of rpkt_gpu_parse_tunnel_ring test the flow
+ *     events first, before n == 0: an empty batch with RPKT_F_FLOW_EV and no event buffer is
+ *     E_INVAL there (an empty slot of a ring is skipped before it) and RPKT_OK from
+ *     rpkt_gpu_parse_batch;
+ *   rpkt_gpu_parse_tunnel_next tests the layout, then that no output aliases its input,
+ *     before frames_bytes;
+ *   rpkt_gpu_fields_batch tests n_req and every request before n == 0;
+ *   rpkt_gpu_parse_options_batch[_compact] tests opts_dev's alignment last, after the flow
+ *     events;
+ *   rpkt_gpu_parse_ring[_compact] tests n_buckets (RPKT_F_FLOW_EV) first in each non-empty
+ *     slot, before the slot's pointers, and the slot's flow_ev_dev last. */
 enum rpkt_err {
     RPKT_OK = 0,
     RPKT_E_INVAL = -1,       /* NULL pointer / zero stride / bad flags            */

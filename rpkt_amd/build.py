@@ -27,7 +27,7 @@ GPU_SRC = [os.path.join(HERE, "csrc", f) for f in
            ("rpkt_parse.hip", "rpkt_tx.hip", "rpkt_walks.hip", "rpkt_fields.hip", "rpkt_tunnel.hip",
             "rpkt_tunnel_chains.hip", "rpkt_tunnel_next.hip", "rpkt_abi.hip", "rpkt_coll.hip")]
 GPU_DEPS = [os.path.join(HERE, "csrc", h) for h in
-            ("rpkt_common.h", "rpkt_opts.h", "rpkt_chain.h", "rpkt_tunnel.h",
+            ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h", "rpkt_chain.h", "rpkt_tunnel.h",
              "rpkt_proto_table.h")]                                   # included; the table is generated
 # units compiled a second time with other defines (same source: same unit hash)
 SECOND_COMPILES = [("rpkt_tx.hip", "rpkt_tx_w64.o", ["-DRPKT_WIN=64", "-DRPKT_TX_W64"]),
@@ -39,13 +39,15 @@ SECOND_COMPILES = [("rpkt_tx.hip", "rpkt_tx_w64.o", ["-DRPKT_WIN=64", "-DRPKT_TX
                                                            "-Wno-unneeded-internal-declaration"])]
 # the csrc headers each unit includes (directly or through another header): a unit's
 # hash covers these, so a change to the option walks' header leaves tx / fields profiles valid
-UNIT_HEADERS = {"rpkt_parse.hip": ("rpkt_common.h", "rpkt_opts.h", "rpkt_chain.h"),
-                "rpkt_tx.hip": ("rpkt_common.h",),
-                "rpkt_walks.hip": ("rpkt_common.h", "rpkt_opts.h", "rpkt_proto_table.h"),
-                "rpkt_fields.hip": ("rpkt_common.h",),
-                "rpkt_tunnel.hip": ("rpkt_common.h", "rpkt_tunnel.h"),
-                "rpkt_tunnel_chains.hip": ("rpkt_common.h", "rpkt_chain.h", "rpkt_tunnel.h"),
-                "rpkt_tunnel_next.hip": ("rpkt_common.h", "rpkt_tunnel.h"),
+UNIT_HEADERS = {"rpkt_parse.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h", "rpkt_chain.h"),
+                "rpkt_tx.hip": ("rpkt_common.h", "rpkt_args.h"),
+                "rpkt_walks.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h",
+                                   "rpkt_proto_table.h"),
+                "rpkt_fields.hip": ("rpkt_common.h", "rpkt_args.h"),
+                "rpkt_tunnel.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_tunnel.h"),
+                "rpkt_tunnel_chains.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_chain.h",
+                                           "rpkt_tunnel.h"),
+                "rpkt_tunnel_next.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_tunnel.h"),
                 "rpkt_abi.hip": ("rpkt_common.h",),
                 "rpkt_coll.hip": ("rpkt_common.h",)}
 # every unit has its header list (a unit added to GPU_SRC without one would make

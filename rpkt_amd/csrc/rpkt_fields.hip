@@ -11,6 +11,7 @@
 // dword loads and a funnel shift; the gather touches one or two lines per layer a request
 // names, so the kernel is latency-bound on those loads, not HBM-bound.
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 
 namespace {
 
@@ -200,7 +201,7 @@ extern "C" {
 int rpkt_gpu_fields_batch(const rpkt_batch_t* b, const rpkt_layers_t* layers_dev,
                           const rpkt_field_req_t* reqs, uint32_t n_req, uint64_t* values_dev,
                           uint32_t* present_dev, void* stream) {
-    if (!b || !layers_dev || !reqs || !values_dev) return RPKT_E_INVAL;
+    if (any_null(b, layers_dev, reqs, values_dev)) return RPKT_E_INVAL;
     if (n_req == 0 || n_req > RPKT_MAX_FIELD_REQS) return RPKT_E_INVAL;
     FieldReqs rq = {};
     uint32_t same_prev = 0;                                 // bit r: request r names the
@@ -215,19 +216,13 @@ int rpkt_gpu_fields_batch(const rpkt_batch_t* b, const rpkt_layers_t* layers_dev
         if (k && t.proto == reqs[k - 1].proto && t.nth == reqs[k - 1].nth) same_prev |= 1u << k;
     }
     for (uint32_t k = n_req + 1; k < RPKT_MAX_FIELD_REQS; ++k) same_prev |= 1u << k;   // padding
-    if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)layers_dev & 15u) != 0 || ((uintptr_t)values_dev & 7u) != 0 ||
-        ((uintptr_t)present_dev & 3u) != 0)
+    if (b->n == 0) return RPKT_OK;          // not the family order: after the requests' checks
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, layers_dev) || misaligned(7, values_dev) || misaligned(3, present_dev))
         return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t grid = (b->n + kFieldBlock - 1) / kFieldBlock;
     const size_t lds = (size_t)kFieldBlock * (2 * kReqGroup + 1) * 4;
-    return launch(fields_kernel, dim3(grid), dim3(kFieldBlock), lds, (hipStream_t)stream,
-                  b->frames_dev, (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n,
-                  layers_dev, rq, n_req, same_prev, values_dev, present_dev);
+    return launch_batch(fields_kernel, kFieldBlock, lds, stream, *b, layers_dev, rq, n_req,
+                        same_prev, values_dev, present_dev);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // (mbuf chains), the flow-counter histogram and reduce, batched checksum::from_slice /
 // from_buf, and the streaming references tools/ablate.py times against the parse.
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 #include "rpkt_chain.h"
 #include "rpkt_opts.h"
 
@@ -740,102 +741,63 @@ __global__ void chain_fold_kernel(const uint32_t* __restrict__ seg_out,
     out[p] = (uint16_t)fold16(acc);
 }
 
-// flags the batch / ring / fused-option parses accept
-constexpr uint32_t kParseFlags = RPKT_F_IP_SUM | RPKT_F_L4_SUM | RPKT_F_FLOW_EV | RPKT_F_IPV6;
-
-// every frame of a strided batch inside the header window from its 16-B boundary (the
-// frame at i * stride has phase (i * stride) & 15: 0 for strides of 16-B multiples)
-inline bool window_fits(const rpkt_batch_t& b, uint32_t win) {
-    const uint32_t flen = b.frame_len ? b.frame_len : b.stride;
-    if (b.offsets_dev || b.stride == 0 || flen == 0) return false;
-    return flen + ((b.stride & 15u) ? 15u : 0u) <= win;
-}
-
-// shared checks of the parse entry points
+// shared checks of the parse entry points, in the family order (RPKT_OK for an empty batch
+// too: the caller returns before it launches)
 int parse_args_ok(const rpkt_batch_t* b, uint32_t flags, const void* recs_dev,
-                         const void* flow_ev_dev, uint32_t n_buckets) {
-    if (!b || !recs_dev) return RPKT_E_INVAL;
-    if (flags & ~kParseFlags) return RPKT_E_INVAL;
+                  const void* flow_ev_dev, uint32_t n_buckets) {
+    if (any_null(b, recs_dev)) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kRxFlags));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0) return RPKT_E_ALIGN;
-    if (flags & RPKT_F_FLOW_EV) {
-        if (!flow_ev_dev || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)
-            return RPKT_E_INVAL;
-        if (((uintptr_t)flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
-    }
-    return 1;
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, recs_dev)) return RPKT_E_ALIGN;
+    return events_ok(flags, flow_ev_dev, n_buckets);
 }
 
 template <bool C16>
 int parse_options(const rpkt_batch_t* b, uint32_t flags, void* recs_dev, rpkt_opts_t* opts_dev,
-                         rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream) {
+                  rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream) {
     if (!opts_dev) return RPKT_E_INVAL;
-    const int ok = parse_args_ok(b, flags, recs_dev, flow_ev_dev, n_buckets);
-    if (ok != 1) return ok;
-    if (((uintptr_t)opts_dev & 15u) != 0) return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
+    RPKT_TRY(parse_args_ok(b, flags, recs_dev, flow_ev_dev, n_buckets));
+    if (b->n == 0) return RPKT_OK;
+    if (misaligned(15, opts_dev)) return RPKT_E_ALIGN;
     auto k = (flags & RPKT_F_L4_SUM) ? parse_kernel<true, 0, C16, true>
                                      : parse_kernel<false, 0, C16, true>;
-    return launch(k, dim3(grid), dim3(per_block), 0, (hipStream_t)stream, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, flags,
-                  (rpkt_rec_t*)recs_dev, (uint64_t*)flow_ev_dev, n_buckets, opts_dev);
+    return launch_batch(k, kWave * kWavesPerBlock, 0, stream, *b, flags, (rpkt_rec_t*)recs_dev,
+                        flow_ev_dev, n_buckets, opts_dev);
 }
 
 template <bool C16>
 int parse_ring(const rpkt_ring_slot_t* slots, uint32_t n_slots, uint32_t flags,
-                      uint32_t n_buckets, void* stream) {
+               uint32_t n_buckets, void* stream) {
     if (n_slots && !slots) return RPKT_E_INVAL;
-    if (flags & ~kParseFlags) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kRxFlags));
     const bool fev = (flags & RPKT_F_FLOW_EV) != 0;
     for (uint32_t k = 0; k < n_slots; ++k) {                      // all checked, then launched
         const rpkt_ring_slot_t& q = slots[k];
         const rpkt_batch_t& b = q.batch;
         if (b.n == 0) continue;                // as rpkt_gpu_parse_batch with n == 0: RPKT_OK
-        if (fev && (n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)) return RPKT_E_INVAL;
-        if (!b.frames_dev || !q.recs_dev) return RPKT_E_INVAL;
-        if (b.frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-        if (!b.offsets_dev && b.stride == 0) return RPKT_E_INVAL;
-        if (((uintptr_t)q.recs_dev & 15u) != 0) return RPKT_E_ALIGN;
-        if (fev && !q.flow_ev_dev) return RPKT_E_INVAL;
-        if (fev && ((uintptr_t)q.flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
+        if (fev) RPKT_TRY(buckets_ok(n_buckets));   // not the family order: before the pointers
+        if (any_null(b.frames_dev, q.recs_dev)) return RPKT_E_INVAL;
+        RPKT_TRY(size_ok(b.frames_bytes));
+        RPKT_TRY(layout_ok(b));
+        if (misaligned(15, q.recs_dev)) return RPKT_E_ALIGN;
+        RPKT_TRY(events_ok(flags, q.flow_ev_dev, n_buckets));
     }
     bool inwin = (flags & RPKT_F_L4_SUM) != 0;                    // every slot's frames in LDS
     for (uint32_t k = 0; inwin && k < n_slots; ++k)
-        inwin = slots[k].batch.n == 0 || window_fits(slots[k].batch, (uint32_t)kWin);
+        inwin = slots[k].batch.n == 0 || fits_window(slots[k].batch, (uint32_t)kWin);
     auto k = !(flags & RPKT_F_L4_SUM) ? parse_ring_kernel<false, C16>
            : inwin                    ? parse_ring_kernel<true, C16, true>
                                       : parse_ring_kernel<true, C16>;
     RingArgs A;
-    uint32_t k0 = 0;
-    while (k0 < n_slots) {
-        A.n_slots = 0;
-        A.tile0[0] = 0;
-        for (; k0 < n_slots && A.n_slots < kRingMax; ++k0) {
-            const rpkt_ring_slot_t& q = slots[k0];
-            const rpkt_batch_t& b = q.batch;
-            if (b.n == 0) continue;
-            RingSlot& S = A.s[A.n_slots];
-            S.frames = b.frames_dev;
-            S.offsets = b.offsets_dev;
-            S.recs = (rpkt_rec_t*)q.recs_dev;
-            S.flow_ev = fev ? (uint64_t*)q.flow_ev_dev : nullptr;
-            S.frames_bytes = (uint32_t)b.frames_bytes;
-            S.stride = b.stride;
-            S.frame_len = b.offsets_dev ? 0u : (b.frame_len ? b.frame_len : b.stride);
-            S.n = b.n;
-            A.tile0[A.n_slots + 1] = A.tile0[A.n_slots] + (b.n + kWave - 1) / kWave;
-            ++A.n_slots;
-        }
-        if (A.n_slots == 0) break;
+    auto outputs = [fev](RingSlot& S, const rpkt_ring_slot_t& q) {
+        S.recs = (rpkt_rec_t*)q.recs_dev;
+        S.flow_ev = fev ? q.flow_ev_dev : nullptr;
+    };
+    for (uint32_t k0 = 0; pack_ring(A, slots, n_slots, k0, outputs);) {
         const uint32_t waves = A.tile0[A.n_slots];
-        const int rc = launch(k, dim3((waves + kRingWPB - 1) / kRingWPB), dim3(kWave * kRingWPB),
-                              0, (hipStream_t)stream, A, flags, n_buckets);
-        if (rc) return rc;
+        RPKT_TRY(launch(k, dim3((waves + kRingWPB - 1) / kRingWPB), dim3(kWave * kRingWPB), 0,
+                        (hipStream_t)stream, A, flags, n_buckets));
     }
     return RPKT_OK;
 }
@@ -864,16 +826,11 @@ __attribute__((visibility("hidden"))) int rpkt_gpu_parse_ring_compact_w64(
 __attribute__((visibility("hidden"))) int rpkt_gpu_parse_batch_compact_w64(
     const rpkt_batch_t* b, uint32_t flags, rpkt_rec16_t* recs_dev, rpkt_flow_ev_t* flow_ev_dev,
     uint32_t n_buckets, void* stream) {
-    const uint32_t flen = b->frame_len ? b->frame_len : b->stride;
-    const uint32_t per_block = kWave * kParseWPB;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
     // the caller checked that every frame lies in its 64-B window: in-window L4 sums
     auto k = (flags & RPKT_F_L4_SUM) ? parse_kernel<true, 0, true, false, kParseWPB, true>
                                      : parse_kernel<false, 0, true, false, kParseWPB>;
-    return launch(k, dim3(grid), dim3(per_block), 0, (hipStream_t)stream, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, flags,
-                  (rpkt_rec_t*)recs_dev, (uint64_t*)flow_ev_dev, n_buckets,
-                  (rpkt_opts_t*)nullptr);
+    return launch_batch(k, kWave * kParseWPB, 0, stream, *b, flags, (rpkt_rec_t*)recs_dev,
+                        flow_ev_dev, n_buckets, nullptr);
 }
 // 80-B records with the L4 sum (RPKT_PARSE_W64_FULL): the record stage keeps the
 // window area at 5376 B, so a wave needs 6.5 KB of LDS instead of 9.7 KB and the
@@ -881,14 +838,10 @@ __attribute__((visibility("hidden"))) int rpkt_gpu_parse_batch_compact_w64(
 __attribute__((visibility("hidden"))) int rpkt_gpu_parse_batch_l4_w64(
     const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* recs_dev, rpkt_flow_ev_t* flow_ev_dev,
     uint32_t n_buckets, void* stream) {
-    const uint32_t flen = b->frame_len ? b->frame_len : b->stride;
-    const uint32_t per_block = kWave * kParseWPB;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
     auto k = (flags & RPKT_F_L4_SUM) ? parse_kernel<true, 0, false, false, kParseWPB, true>
                                      : parse_kernel<false, 0, false, false, kParseWPB>;
-    return launch(k, dim3(grid), dim3(per_block), 0, (hipStream_t)stream, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, flags,
-                  recs_dev, (uint64_t*)flow_ev_dev, n_buckets, (rpkt_opts_t*)nullptr);
+    return launch_batch(k, kWave * kParseWPB, 0, stream, *b, flags, recs_dev, flow_ev_dev,
+                        n_buckets, nullptr);
 }
 #else
 int rpkt_gpu_parse_batch_compact_w64(const rpkt_batch_t*, uint32_t, rpkt_rec16_t*,
@@ -899,12 +852,6 @@ int rpkt_gpu_parse_batch_l4_w64(const rpkt_batch_t*, uint32_t, rpkt_rec_t*, rpkt
 #define RPKT_PARSE_W64_FULL 1
 #endif
 int rpkt_gpu_parse_ring_compact_w64(const rpkt_ring_slot_t*, uint32_t, uint32_t, uint32_t, void*);
-
-// every frame of a strided batch inside a 64-B window from its 16-B boundary
-static bool parse_w64_fits(const rpkt_batch_t* b, uint32_t flen) {
-    if (b->offsets_dev || b->stride == 0 || flen == 0) return false;
-    return flen + ((b->stride & 15u) ? 15u : 0u) <= 64u;
-}
 
 uint32_t rpkt_flow_hash(uint32_t ip_src, uint32_t ip_dst, uint16_t sp, uint16_t dp,
                         uint8_t proto) {
@@ -923,30 +870,16 @@ uint32_t rpkt_flow_hash(uint32_t ip_src, uint32_t ip_dst, uint16_t sp, uint16_t 
 
 int rpkt_gpu_parse_batch(const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* recs_dev,
                          rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream) {
-    if (!b || !recs_dev) return RPKT_E_INVAL;
-    if (flags & ~kParseFlags) return RPKT_E_INVAL;
+    RPKT_TRY(parse_args_ok(b, flags, recs_dev, flow_ev_dev, n_buckets));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0) return RPKT_E_ALIGN;
-    if (flags & RPKT_F_FLOW_EV) {
-        if (!flow_ev_dev || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)
-            return RPKT_E_INVAL;
-        if (((uintptr_t)flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
-    }
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
     if (RPKT_PARSE_W64_ON && RPKT_PARSE_W64_FULL && ((flags & RPKT_F_L4_SUM) || RPKT_PARSE_W64_FULL > 1) &&
-        parse_w64_fits(b, flen))
+        fits_window(*b, 64))
         return rpkt_gpu_parse_batch_l4_w64(b, flags, recs_dev, flow_ev_dev, n_buckets, stream);
-    const uint32_t per_block = kWave * kParseWPB;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
     auto k = !(flags & RPKT_F_L4_SUM)     ? parse_kernel<false, 0, false, false, kParseWPB>
-           : window_fits(*b, (uint32_t)kWin) ? parse_kernel<true, 0, false, false, kParseWPB, true>
+           : fits_window(*b, (uint32_t)kWin) ? parse_kernel<true, 0, false, false, kParseWPB, true>
                                             : parse_kernel<true, 0, false, false, kParseWPB>;
-    return launch(k, dim3(grid), dim3(per_block), 0, (hipStream_t)stream, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, flags,
-                  recs_dev, (uint64_t*)flow_ev_dev, n_buckets, (rpkt_opts_t*)nullptr);
+    return launch_batch(k, kWave * kParseWPB, 0, stream, *b, flags, recs_dev, flow_ev_dev,
+                        n_buckets, nullptr);
 }
 
 int rpkt_gpu_parse_ring(const rpkt_ring_slot_t* slots, uint32_t n_slots, uint32_t flags,
@@ -959,40 +892,23 @@ int rpkt_gpu_parse_ring_compact(const rpkt_ring_slot_t* slots, uint32_t n_slots,
     // a ring whose every slot is a strided batch of short frames goes to the 64-B-window
     // compile, as rpkt_gpu_parse_batch_compact hands such a batch over
     bool w64 = RPKT_PARSE_W64_ON && slots && n_slots;
-    for (uint32_t k = 0; w64 && k < n_slots; ++k) {
-        const rpkt_batch_t& b = slots[k].batch;
-        w64 = b.n == 0 || parse_w64_fits(&b, b.frame_len ? b.frame_len : b.stride);
-    }
+    for (uint32_t k = 0; w64 && k < n_slots; ++k)
+        w64 = slots[k].batch.n == 0 || fits_window(slots[k].batch, 64);
     return w64 ? rpkt_gpu_parse_ring_compact_w64(slots, n_slots, flags, n_buckets, stream)
                : parse_ring<true>(slots, n_slots, flags, n_buckets, stream);
 }
 
 int rpkt_gpu_parse_batch_compact(const rpkt_batch_t* b, uint32_t flags, rpkt_rec16_t* recs_dev,
                                  rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream) {
-    if (!b || !recs_dev) return RPKT_E_INVAL;
-    if (flags & ~kParseFlags) return RPKT_E_INVAL;
+    RPKT_TRY(parse_args_ok(b, flags, recs_dev, flow_ev_dev, n_buckets));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0) return RPKT_E_ALIGN;
-    if (flags & RPKT_F_FLOW_EV) {
-        if (!flow_ev_dev || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)
-            return RPKT_E_INVAL;
-        if (((uintptr_t)flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
-    }
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    if (RPKT_PARSE_W64_ON && parse_w64_fits(b, flen))
+    if (RPKT_PARSE_W64_ON && fits_window(*b, 64))
         return rpkt_gpu_parse_batch_compact_w64(b, flags, recs_dev, flow_ev_dev, n_buckets, stream);
-    const uint32_t per_block = kWave * kParseWPB;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
     auto k = !(flags & RPKT_F_L4_SUM)     ? parse_kernel<false, 0, true, false, kParseWPB>
-           : window_fits(*b, (uint32_t)kWin) ? parse_kernel<true, 0, true, false, kParseWPB, true>
+           : fits_window(*b, (uint32_t)kWin) ? parse_kernel<true, 0, true, false, kParseWPB, true>
                                             : parse_kernel<true, 0, true, false, kParseWPB>;
-    return launch(k, dim3(grid), dim3(per_block), 0, (hipStream_t)stream, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, flags,
-                  (rpkt_rec_t*)recs_dev, (uint64_t*)flow_ev_dev, n_buckets,
-                  (rpkt_opts_t*)nullptr);
+    return launch_batch(k, kWave * kParseWPB, 0, stream, *b, flags, (rpkt_rec_t*)recs_dev,
+                        flow_ev_dev, n_buckets, nullptr);
 }
 
 int rpkt_gpu_parse_options_batch(const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* recs_dev,
@@ -1010,17 +926,12 @@ int rpkt_gpu_parse_options_batch_compact(const rpkt_batch_t* b, uint32_t flags,
 
 int rpkt_gpu_parse_chains(const rpkt_chains_t* c, uint32_t flags, rpkt_rec_t* recs_dev,
                           rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream) {
-    if (!c || !recs_dev) return RPKT_E_INVAL;
-    if (flags & ~kParseFlags) return RPKT_E_INVAL;
+    if (any_null(c, recs_dev)) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kRxFlags));
     if (c->n_chains == 0) return RPKT_OK;
-    if (!c->chain_first_dev || (c->n_segs && (!c->buf_dev || !c->segs_dev))) return RPKT_E_INVAL;
-    if (c->buf_bytes > kMaxFrameBytes || c->n_segs >= 0x80000000u) return RPKT_E_TOO_LARGE;
-    if (((uintptr_t)recs_dev & 15u) != 0 || ((uintptr_t)c->segs_dev & 7u) != 0) return RPKT_E_ALIGN;
-    if (flags & RPKT_F_FLOW_EV) {
-        if (!flow_ev_dev || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)
-            return RPKT_E_INVAL;
-        if (((uintptr_t)flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
-    }
+    RPKT_TRY(chains_ok(*c));
+    if (misaligned(15, recs_dev) || misaligned(7, c->segs_dev)) return RPKT_E_ALIGN;
+    RPKT_TRY(events_ok(flags, flow_ev_dev, n_buckets));
     const uint32_t per_block = kWave * kWavesPerBlock;
     const uint32_t grid = (c->n_chains + per_block - 1) / per_block;
     auto k = (flags & RPKT_F_L4_SUM) ? parse_chains_kernel<true> : parse_chains_kernel<false>;
@@ -1037,15 +948,12 @@ int rpkt_gpu_parse_chains(const rpkt_chains_t* c, uint32_t flags, rpkt_rec_t* re
 int rpkt_gpu_debug_variant(const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* recs, int variant,
                            void* stream) {
     if (!b || !recs || b->n == 0) return RPKT_E_INVAL;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
     const uint32_t per_block = kWave * kWavesPerBlock;
     const uint32_t grid = (b->n + per_block - 1) / per_block;
     hipStream_t st = (hipStream_t)stream;
-#define RPKT_V(v)                                                                       \
-    launch((flags & RPKT_F_L4_SUM) ? parse_kernel<true, v> : parse_kernel<false, v>,   \
-           dim3(grid), dim3(per_block), 0, st, b->frames_dev, (uint32_t)b->frames_bytes,   \
-           b->offsets_dev, b->stride, flen, b->n, flags, recs, (uint64_t*)nullptr, 0u,      \
-           (rpkt_opts_t*)nullptr)
+#define RPKT_V(v)                                                                           \
+    launch_batch((flags & RPKT_F_L4_SUM) ? parse_kernel<true, v> : parse_kernel<false, v>, \
+                 per_block, 0, stream, *b, flags, recs, nullptr, 0u, nullptr)
     switch (variant) {
         case 0: return RPKT_V(0);
         case 1: return RPKT_V(1);
@@ -1117,17 +1025,13 @@ int rpkt_gpu_debug_variant(const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* re
 extern "C++" template <int WPB>
 int launch_stamps(const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* recs, void* stamps_dev,
                   hipStream_t st) {
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t per_block = kWave * WPB;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
     const bool l4 = (flags & RPKT_F_L4_SUM) != 0;
     auto k = stamps_dev ? (l4 ? parse_kernel<true, 50, false, false, WPB>
                               : parse_kernel<false, 50, false, false, WPB>)
                         : (l4 ? parse_kernel<true, 0, false, false, WPB>
                               : parse_kernel<false, 0, false, false, WPB>);
-    return launch(k, dim3(grid), dim3(per_block), 0, st, b->frames_dev, (uint32_t)b->frames_bytes,
-                  b->offsets_dev, b->stride, flen, b->n, flags & kParseFlags, recs,
-                  (uint64_t*)stamps_dev, 0u, (rpkt_opts_t*)nullptr);
+    return launch_batch(k, kWave * WPB, 0, st, *b, flags & kRxFlags, recs, (uint64_t*)stamps_dev,
+                        0u, nullptr);
 }
 int rpkt_gpu_debug_stamps(const rpkt_batch_t* b, uint32_t flags, rpkt_rec_t* recs,
                           void* stamps_dev, int wpb, void* stream) {
@@ -1174,7 +1078,7 @@ size_t rpkt_gpu_flow_workspace_bytes(uint32_t n, uint32_t n_buckets) {
 
 int rpkt_gpu_flow_count(const rpkt_flow_ev_t* ev, uint32_t n, uint32_t n_buckets,
                         uint64_t* counters, void* workspace, void* stream) {
-    if (!counters || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS) return RPKT_E_INVAL;
+    if (!counters || buckets_ok(n_buckets) != RPKT_OK) return RPKT_E_INVAL;
     if (n == 0) return RPKT_OK;
     if (!ev) return RPKT_E_INVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -1202,8 +1106,8 @@ int rpkt_gpu_flow_count(const rpkt_flow_ev_t* ev, uint32_t n, uint32_t n_buckets
 int rpkt_gpu_checksum_ranges(const uint8_t* buf, uint64_t buf_bytes, const uint32_t* ranges,
                              uint32_t n, uint16_t* out, void* stream) {
     if (n == 0) return RPKT_OK;
-    if (!buf || !ranges || !out) return RPKT_E_INVAL;
-    if (buf_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
+    if (any_null(buf, ranges, out)) return RPKT_E_INVAL;
+    RPKT_TRY(size_ok(buf_bytes));
     const uint32_t per_block = kWave * kWavesPerBlock;
     return launch(checksum_ranges_kernel, dim3((n + per_block - 1) / per_block), dim3(per_block),
                   0, (hipStream_t)stream, buf, (uint32_t)buf_bytes, ranges, n, out);
@@ -1217,8 +1121,9 @@ int rpkt_gpu_checksum_chains(const uint8_t* buf, uint64_t buf_bytes, const uint3
                              uint32_t n_segs, const uint32_t* chain_first, uint32_t n_chains,
                              uint16_t* out, void* workspace, void* stream) {
     if (n_chains == 0) return RPKT_OK;
-    if (!chain_first || !out || (n_segs && (!buf || !segs || !workspace))) return RPKT_E_INVAL;
-    if (buf_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
+    if (any_null(chain_first, out) || (n_segs && any_null(buf, segs, workspace)))
+        return RPKT_E_INVAL;
+    RPKT_TRY(size_ok(buf_bytes));
     hipStream_t st = (hipStream_t)stream;
     const uint32_t per_block = kWave * kWavesPerBlock;
     if (n_segs) {

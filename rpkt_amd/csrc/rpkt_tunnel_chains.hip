@@ -17,6 +17,7 @@
 // stream (inner headers past the window) and after the inner packet (padding, GTP trailing
 // bytes) get a pass each, which returns at once when no lane of the wave has such bytes.
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 #include "rpkt_chain.h"
 #include "rpkt_tunnel.h"
 
@@ -446,8 +447,6 @@ void tunnel_chains_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
                                            reinterpret_cast<u32x4*>(tun) + i);
 }
 
-constexpr uint32_t kTunChainFlags = RPKT_F_IP_SUM | RPKT_F_L4_SUM | RPKT_F_IPV6 | RPKT_F_FLOW_EV;
-
 }  // namespace
 
 extern "C" {
@@ -456,19 +455,13 @@ int rpkt_gpu_parse_tunnel_chains(const rpkt_chains_t* c, uint32_t flags, rpkt_re
                                  rpkt_tun_t* tun_dev, rpkt_rec_t* inner_dev,
                                  rpkt_flow_ev_t* flow_ev_dev, uint32_t n_buckets, void* stream) {
     if (!c) return RPKT_E_INVAL;
-    if (flags & ~kTunChainFlags) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kRxFlags));
     if (c->n_chains == 0) return RPKT_OK;
-    if (!outer_dev || !tun_dev || !inner_dev) return RPKT_E_INVAL;
-    if (!c->chain_first_dev || (c->n_segs && (!c->buf_dev || !c->segs_dev))) return RPKT_E_INVAL;
-    if (c->buf_bytes > kMaxFrameBytes || c->n_segs >= 0x80000000u) return RPKT_E_TOO_LARGE;
-    if ((((uintptr_t)outer_dev | (uintptr_t)tun_dev | (uintptr_t)inner_dev) & 15u) != 0 ||
-        ((uintptr_t)c->segs_dev & 7u) != 0)
+    if (any_null(outer_dev, tun_dev, inner_dev)) return RPKT_E_INVAL;
+    RPKT_TRY(chains_ok(*c));
+    if (misaligned(15, outer_dev, tun_dev, inner_dev) || misaligned(7, c->segs_dev))
         return RPKT_E_ALIGN;
-    if (flags & RPKT_F_FLOW_EV) {
-        if (!flow_ev_dev || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)
-            return RPKT_E_INVAL;
-        if (((uintptr_t)flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
-    }
+    RPKT_TRY(events_ok(flags, flow_ev_dev, n_buckets));
     const uint32_t grid = (c->n_chains + kWave - 1) / kWave;
     auto k = (flags & RPKT_F_L4_SUM) ? tunnel_chains_kernel<true> : tunnel_chains_kernel<false>;
     return launch(k, dim3(grid), dim3(kWave), 0, (hipStream_t)stream, c->buf_dev,

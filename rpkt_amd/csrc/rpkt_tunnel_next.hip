@@ -14,6 +14,7 @@
 // for a nested frame the innermost L4 bytes were streamed once by level 1 (for the
 // mid-level sum) and are read here a second time.
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 #include "rpkt_tunnel.h"
 
 namespace {
@@ -148,8 +149,6 @@ void tunnel_next_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
                                            reinterpret_cast<u32x4*>(tun_next) + i);
 }
 
-constexpr uint32_t kNextFlags = RPKT_F_IP_SUM | RPKT_F_L4_SUM | RPKT_F_IPV6 | RPKT_F_FLOW_EV;
-
 }  // namespace
 
 extern "C" {
@@ -159,27 +158,18 @@ int rpkt_gpu_parse_tunnel_next(const rpkt_batch_t* b, uint32_t flags, const rpkt
                                rpkt_rec_t* inner_next_dev, rpkt_flow_ev_t* flow_ev_dev,
                                uint32_t n_buckets, void* stream) {
     if (!b) return RPKT_E_INVAL;
-    if (flags & ~kNextFlags) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kRxFlags));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev || !tun_dev || !inner_dev || !tun_next_dev || !inner_next_dev)
+    if (any_null(b->frames_dev, tun_dev, inner_dev, tun_next_dev, inner_next_dev))
         return RPKT_E_INVAL;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
+    RPKT_TRY(layout_ok(*b));                // not the family order: layout and aliasing before size
     if (tun_next_dev == tun_dev || inner_next_dev == inner_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if ((((uintptr_t)tun_dev | (uintptr_t)inner_dev | (uintptr_t)tun_next_dev |
-          (uintptr_t)inner_next_dev) & 15u) != 0)
-        return RPKT_E_ALIGN;
-    if (flags & RPKT_F_FLOW_EV) {
-        if (!flow_ev_dev || n_buckets == 0 || n_buckets > RPKT_FLOW_MAX_BUCKETS)
-            return RPKT_E_INVAL;
-        if (((uintptr_t)flow_ev_dev & 7u) != 0) return RPKT_E_ALIGN;
-    }
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t grid = (b->n + kWave - 1) / kWave;
+    RPKT_TRY(size_ok(b->frames_bytes));
+    if (misaligned(15, tun_dev, inner_dev, tun_next_dev, inner_next_dev)) return RPKT_E_ALIGN;
+    RPKT_TRY(events_ok(flags, flow_ev_dev, n_buckets));
     auto k = (flags & RPKT_F_L4_SUM) ? tunnel_next_kernel<true> : tunnel_next_kernel<false>;
-    return launch(k, dim3(grid), dim3(kWave), 0, (hipStream_t)stream, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, flags, tun_dev,
-                  inner_dev, tun_next_dev, inner_next_dev, (uint64_t*)flow_ev_dev, n_buckets);
+    return launch_batch(k, kWave, 0, stream, *b, flags, tun_dev, inner_dev, tun_next_dev,
+                        inner_next_dev, flow_ev_dev, n_buckets);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // rpkt_tx.hip — transmit side: build_kernel (prepend_header + setters + checksum fill)
 // and forward_kernel (the loopback_rx firewall loop fused into one pass).
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 
 namespace {
 
@@ -674,36 +675,23 @@ int rpkt_gpu_debug_forward_variant_w64(const rpkt_batch_t*, const rpkt_fwd_t*, u
 #endif
 #endif
 
-#ifndef RPKT_TX_W64
-// strided, every frame within 64 bytes of its 16-B boundary: the 64-B-window compile
-static bool tx_w64_fits(const rpkt_batch_t* b, uint32_t flen) {
-    if (b->offsets_dev || b->stride == 0 || flen == 0) return false;
-    return flen + ((b->stride & 15u) ? 15u : 0u) <= 64u;
-}
-#endif
+// flags rpkt_gpu_build_batch and rpkt_gpu_build_tunnel_batch accept
+constexpr uint32_t kBuildFlags = RPKT_BUILD_IP_CSUM | RPKT_BUILD_L4_CSUM;
 
 int RPKT_TX_FN(rpkt_gpu_build_batch)(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                                      uint32_t flags, uint8_t* built_dev, void* stream) {
-    if (!b || !recs_dev) return RPKT_E_INVAL;
-    if (flags & ~(uint32_t)(RPKT_BUILD_IP_CSUM | RPKT_BUILD_L4_CSUM)) return RPKT_E_INVAL;
+    if (any_null(b, recs_dev)) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kBuildFlags));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0 || ((uintptr_t)b->frames_dev & 15u) != 0)
-        return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, recs_dev, b->frames_dev)) return RPKT_E_ALIGN;
 #ifndef RPKT_TX_W64
-    if (RPKT_TX_W64_ON && tx_w64_fits(b, flen))
+    if (RPKT_TX_W64_ON && fits_window(*b, 64))
         return rpkt_gpu_build_batch_w64(b, recs_dev, flags, built_dev, stream);
 #endif
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
     auto k = (flags & RPKT_BUILD_L4_CSUM) ? build_kernel<true> : build_kernel<false>;
-    return launch(k, dim3(grid), dim3(per_block), kTxLdsPad, (hipStream_t)stream,
-                  const_cast<uint8_t*>(b->frames_dev), (uint32_t)b->frames_bytes, b->offsets_dev,
-                  b->stride, flen, b->n, recs_dev, flags, built_dev,
-                  static_cast<const rpkt_tun_t*>(nullptr));
+    return launch_batch(k, kWave * kWavesPerBlock, kTxLdsPad, stream, *b, recs_dev, flags,
+                        built_dev, nullptr);
 }
 
 #ifndef RPKT_TX_W64
@@ -712,46 +700,33 @@ int RPKT_TX_FN(rpkt_gpu_build_batch)(const rpkt_batch_t* b, const rpkt_rec_t* re
 int rpkt_gpu_build_tunnel_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                                 const rpkt_tun_t* tun_dev, uint32_t flags, uint8_t* built_dev,
                                 void* stream) {
-    if (!b || !recs_dev || !tun_dev) return RPKT_E_INVAL;
-    if (flags & ~(uint32_t)(RPKT_BUILD_IP_CSUM | RPKT_BUILD_L4_CSUM)) return RPKT_E_INVAL;
+    if (any_null(b, recs_dev, tun_dev)) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, kBuildFlags));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0 || ((uintptr_t)tun_dev & 15u) != 0 ||
-        ((uintptr_t)b->frames_dev & 15u) != 0)
-        return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, recs_dev, tun_dev, b->frames_dev)) return RPKT_E_ALIGN;
     auto k = (flags & RPKT_BUILD_L4_CSUM) ? build_kernel<true, true> : build_kernel<false, true>;
-    return launch(k, dim3(grid), dim3(per_block), kTxLdsPad, (hipStream_t)stream,
-                  const_cast<uint8_t*>(b->frames_dev), (uint32_t)b->frames_bytes, b->offsets_dev,
-                  b->stride, flen, b->n, recs_dev, flags, built_dev, tun_dev);
+    return launch_batch(k, kWave * kWavesPerBlock, kTxLdsPad, stream, *b, recs_dev, flags,
+                        built_dev, tun_dev);
 }
 #endif
 
 int RPKT_TX_FN(rpkt_gpu_forward_batch)(const rpkt_batch_t* b, const rpkt_fwd_t* fwd,
                                        uint8_t* keep_dev, void* stream) {
-    if (!b || !fwd || !keep_dev) return RPKT_E_INVAL;
+    if (any_null(b, fwd, keep_dev)) return RPKT_E_INVAL;
     // unknown bits (a caller that left the old `reserved` field uninitialised) are refused,
     // as rpkt_gpu_build_batch refuses unknown build flags
-    if (fwd->flags & ~(uint32_t)RPKT_F_IPV6) return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(fwd->flags, RPKT_F_IPV6));
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev || (fwd->n_forbid && !fwd->forbid_dev)) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)b->frames_dev & 15u) != 0) return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
+    if (fwd->n_forbid && !fwd->forbid_dev) return RPKT_E_INVAL;
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, b->frames_dev)) return RPKT_E_ALIGN;
 #ifndef RPKT_TX_W64
-    if (RPKT_TX_W64_ON && tx_w64_fits(b, flen))
+    if (RPKT_TX_W64_ON && fits_window(*b, 64))
         return rpkt_gpu_forward_batch_w64(b, fwd, keep_dev, stream);
 #endif
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
-    return launch(forward_kernel<0>, dim3(grid), dim3(per_block), kTxLdsPad, (hipStream_t)stream,
-                  const_cast<uint8_t*>(b->frames_dev), (uint32_t)b->frames_bytes, b->offsets_dev,
-                  b->stride, flen, b->n, *fwd, keep_dev);
+    return launch_batch(forward_kernel<0>, kWave * kWavesPerBlock, kTxLdsPad, stream, *b, *fwd,
+                        keep_dev);
 }
 
 #ifdef RPKT_ABLATE
@@ -759,27 +734,16 @@ int RPKT_TX_FN(rpkt_gpu_forward_batch)(const rpkt_batch_t* b, const rpkt_fwd_t* 
 // forward_kernel ablation variants for tools/ablate_fwd.py.
 int RPKT_TX_FN(rpkt_gpu_debug_forward_variant)(const rpkt_batch_t* b, const rpkt_fwd_t* fwd,
                                                uint8_t* keep_dev, int variant, void* stream) {
-    if (!b || !fwd || !keep_dev || b->n == 0) return RPKT_E_INVAL;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
+    if (any_null(b, fwd, keep_dev) || b->n == 0) return RPKT_E_INVAL;
+#define RPKT_FV(v) \
+    launch_batch(forward_kernel<v>, kWave * kWavesPerBlock, kTxLdsPad, stream, *b, *fwd, keep_dev)
 #ifndef RPKT_TX_W64
     if (variant >= 10) {                          // the 64-B-window compile's variants
-        if (!tx_w64_fits(b, flen)) return RPKT_E_INVAL;
+        if (!fits_window(*b, 64)) return RPKT_E_INVAL;
         return rpkt_gpu_debug_forward_variant_w64(b, fwd, keep_dev, variant - 10, stream);
     }
-    if (variant == 9) {                           // the product path of this compile only
-        const uint32_t per_block = kWave * kWavesPerBlock;
-        return launch(forward_kernel<0>, dim3((b->n + per_block - 1) / per_block), dim3(per_block), kTxLdsPad,
-                      (hipStream_t)stream, const_cast<uint8_t*>(b->frames_dev),
-                      (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n, *fwd,
-                      keep_dev);
-    }
+    if (variant == 9) return RPKT_FV(0);          // the product path of this compile only
 #endif
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
-#define RPKT_FV(v)                                                                          \
-    launch(forward_kernel<v>, dim3(grid), dim3(per_block), kTxLdsPad, (hipStream_t)stream,          \
-           const_cast<uint8_t*>(b->frames_dev), (uint32_t)b->frames_bytes, b->offsets_dev,  \
-           b->stride, flen, b->n, *fwd, keep_dev)
     switch (variant) {
         case 0: return RPKT_FV(0);
         case 1: return RPKT_FV(1);

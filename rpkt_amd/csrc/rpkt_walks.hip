@@ -1,6 +1,7 @@
 // rpkt_walks.hip — per-frame walks over a batch: the IPv4/TCP option iterators and the
 // protocol-layer walk driven by the pktfmt-derived table.
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 #include "rpkt_opts.h"
 #include "rpkt_proto_table.h"
 
@@ -1137,7 +1138,7 @@ int resident_blocks(const void* k, uint32_t block_threads, uint32_t& out) {
 // resident blocks (each block walks ceil(n / resident) frames, at least its waves'
 // first tiles); F > 0: pools of 64 F frames per wave (kLayFrames, the ablations).
 template <int F, bool DYN = false, int ABL = 0>
-int launch_layers(const rpkt_batch_t* b, uint32_t flen, rpkt_layers_t* layers_dev, void* stream) {
+int launch_layers(const rpkt_batch_t* b, rpkt_layers_t* layers_dev, void* stream) {
     const uint32_t per_block = kWave * kWavesPerBlock;
     uint32_t pool = per_block * (F > 0 ? F : 1), grid;
     if constexpr (F == 0) {
@@ -1153,8 +1154,19 @@ int launch_layers(const rpkt_batch_t* b, uint32_t flen, rpkt_layers_t* layers_de
         grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     }
     return launch(layers_kernel<F, DYN, ABL>, dim3(grid), dim3(per_block), 0, (hipStream_t)stream,
-                  b->frames_dev, (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n,
-                  layers_dev, pool);
+                  b->frames_dev, (uint32_t)b->frames_bytes, b->offsets_dev, b->stride,
+                  batch_flen(*b), b->n, layers_dev, pool);
+}
+
+template <bool C16>
+int options_batch(const rpkt_batch_t* b, const void* recs_dev, rpkt_opts_t* opts_dev,
+                  void* stream) {
+    if (any_null(b, recs_dev, opts_dev)) return RPKT_E_INVAL;
+    if (b->n == 0) return RPKT_OK;
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, recs_dev, opts_dev)) return RPKT_E_ALIGN;
+    return launch_batch(options_kernel<C16>, kWave * kWavesPerBlock, 0, stream, *b, recs_dev,
+                        opts_dev);
 }
 
 }  // namespace
@@ -1163,48 +1175,23 @@ extern "C" {
 
 int rpkt_gpu_options_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                            rpkt_opts_t* opts_dev, void* stream) {
-    if (!b || !recs_dev || !opts_dev) return RPKT_E_INVAL;
-    if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0 || ((uintptr_t)opts_dev & 15u) != 0) return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
-    return launch(options_kernel<false>, dim3(grid), dim3(per_block), 0, (hipStream_t)stream,
-                  b->frames_dev, (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n,
-                  (const void*)recs_dev, opts_dev);
+    return options_batch<false>(b, recs_dev, opts_dev, stream);
 }
 
 int rpkt_gpu_options_batch_compact(const rpkt_batch_t* b, const rpkt_rec16_t* recs_dev,
                                    rpkt_opts_t* opts_dev, void* stream) {
-    if (!b || !recs_dev || !opts_dev) return RPKT_E_INVAL;
-    if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)recs_dev & 15u) != 0 || ((uintptr_t)opts_dev & 15u) != 0) return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
-    const uint32_t per_block = kWave * kWavesPerBlock;
-    const uint32_t grid = (b->n + per_block - 1) / per_block;
-    return launch(options_kernel<true>, dim3(grid), dim3(per_block), 0, (hipStream_t)stream,
-                  b->frames_dev, (uint32_t)b->frames_bytes, b->offsets_dev, b->stride, flen, b->n,
-                  (const void*)recs_dev, opts_dev);
+    return options_batch<true>(b, recs_dev, opts_dev, stream);
 }
 
 int rpkt_gpu_layers_batch(const rpkt_batch_t* b, rpkt_layers_t* layers_dev, void* stream) {
-    if (!b || !layers_dev) return RPKT_E_INVAL;
+    if (any_null(b, layers_dev)) return RPKT_E_INVAL;
     if (b->n == 0) return RPKT_OK;
-    if (!b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    if (((uintptr_t)layers_dev & 15u) != 0) return RPKT_E_ALIGN;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
+    RPKT_TRY(batch_ok(*b));
+    if (misaligned(15, layers_dev)) return RPKT_E_ALIGN;
 #if RPKT_LAY_RUNTIME_POOL
-    return launch_layers<0, true>(b, flen, layers_dev, stream);
+    return launch_layers<0, true>(b, layers_dev, stream);
 #else
-    return launch_layers<kLayFrames, true>(b, flen, layers_dev, stream);
+    return launch_layers<kLayFrames, true>(b, layers_dev, stream);
 #endif
 }
 
@@ -1217,26 +1204,24 @@ int rpkt_gpu_layers_batch(const rpkt_batch_t* b, rpkt_layers_t* layers_dev, void
 // on the capture mix, whose waves hold many groups per step.)
 int rpkt_gpu_debug_layers_variant(const rpkt_batch_t* b, rpkt_layers_t* layers_dev, int frames,
                                   void* stream) {
-    if (!b || !layers_dev || b->n == 0 || !b->frames_dev) return RPKT_E_INVAL;
-    if (b->frames_bytes > kMaxFrameBytes) return RPKT_E_TOO_LARGE;
-    if (!b->offsets_dev && b->stride == 0) return RPKT_E_INVAL;
-    const uint32_t flen = b->offsets_dev ? 0 : (b->frame_len ? b->frame_len : b->stride);
+    if (any_null(b, layers_dev) || b->n == 0) return RPKT_E_INVAL;
+    RPKT_TRY(batch_ok(*b));
     switch (frames) {
-        case 1: return launch_layers<1>(b, flen, layers_dev, stream);
-        case 2: return launch_layers<2>(b, flen, layers_dev, stream);
-        case 4: return launch_layers<4>(b, flen, layers_dev, stream);
-        case 8: return launch_layers<8>(b, flen, layers_dev, stream);
-        case 104: return launch_layers<4, true>(b, flen, layers_dev, stream);   // pooled
-        case 102: return launch_layers<2, true>(b, flen, layers_dev, stream);
-        case 108: return launch_layers<8, true>(b, flen, layers_dev, stream);
-        case 201: return launch_layers<4, true, 1>(b, flen, layers_dev, stream);  // ablations
-        case 202: return launch_layers<4, true, 2>(b, flen, layers_dev, stream);
-        case 203: return launch_layers<4, true, 3>(b, flen, layers_dev, stream);
-        case 204: return launch_layers<4, true, 4>(b, flen, layers_dev, stream);
-        case 205: return launch_layers<4, true, 5>(b, flen, layers_dev, stream);
-        case 206: return launch_layers<4, true, 6>(b, flen, layers_dev, stream);
-        case 207: return launch_layers<4, true, 7>(b, flen, layers_dev, stream);
-        case 300: return launch_layers<0, true>(b, flen, layers_dev, stream);     // run-time pools
+        case 1: return launch_layers<1>(b, layers_dev, stream);
+        case 2: return launch_layers<2>(b, layers_dev, stream);
+        case 4: return launch_layers<4>(b, layers_dev, stream);
+        case 8: return launch_layers<8>(b, layers_dev, stream);
+        case 104: return launch_layers<4, true>(b, layers_dev, stream);   // pooled
+        case 102: return launch_layers<2, true>(b, layers_dev, stream);
+        case 108: return launch_layers<8, true>(b, layers_dev, stream);
+        case 201: return launch_layers<4, true, 1>(b, layers_dev, stream);  // ablations
+        case 202: return launch_layers<4, true, 2>(b, layers_dev, stream);
+        case 203: return launch_layers<4, true, 3>(b, layers_dev, stream);
+        case 204: return launch_layers<4, true, 4>(b, layers_dev, stream);
+        case 205: return launch_layers<4, true, 5>(b, layers_dev, stream);
+        case 206: return launch_layers<4, true, 6>(b, layers_dev, stream);
+        case 207: return launch_layers<4, true, 7>(b, layers_dev, stream);
+        case 300: return launch_layers<0, true>(b, layers_dev, stream);     // run-time pools
         default: return RPKT_E_INVAL;
     }
 }

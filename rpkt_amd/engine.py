@@ -55,20 +55,52 @@ class Fwd(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
-EXPORTS = ["rpkt_gpu_abi_version", "rpkt_gpu_build_info", "rpkt_gpu_status_name",
-           "rpkt_gpu_last_hip_error", "rpkt_gpu_device_info", "rpkt_gpu_parse_batch", "rpkt_gpu_flow_workspace_bytes",
-           "rpkt_gpu_flow_count", "rpkt_gpu_checksum_ranges", "rpkt_flow_hash",
-           "rpkt_gpu_checksum_chains_workspace_bytes", "rpkt_gpu_checksum_chains",
-           "rpkt_gpu_parse_chains", "rpkt_gpu_build_batch", "rpkt_gpu_forward_batch",
-           "rpkt_gpu_options_batch", "rpkt_gpu_layers_batch", "rpkt_gpu_fields_batch",
-           "rpkt_gpu_flow_reduce", "rpkt_gpu_last_coll_error", "rpkt_gpu_coll_version",
-           "rpkt_gpu_parse_batch_compact", "rpkt_gpu_options_batch_compact",
-           "rpkt_gpu_parse_options_batch", "rpkt_gpu_parse_options_batch_compact",
-           "rpkt_gpu_parse_ring", "rpkt_gpu_parse_ring_compact", "rpkt_gpu_coll_unique_id",
-           "rpkt_gpu_comm_init", "rpkt_gpu_comm_destroy", "rpkt_gpu_comm_init_timeout",
-           "rpkt_gpu_comm_abort", "rpkt_gpu_parse_tunnel_batch", "rpkt_gpu_build_tunnel_batch",
-           "rpkt_gpu_parse_tunnel_ring", "rpkt_gpu_parse_tunnel_chains",
-           "rpkt_gpu_parse_tunnel_next"]
+_i, _u32, _p, _sz = ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t
+_B, _C = ctypes.POINTER(Batch), ctypes.POINTER(Chains)
+_PARSE = [_B, _u32, _p, _p, _u32, _p]                 # batch, flags, recs, events, buckets, stream
+_RING = [_u32, _u32, _u32, _p]                        # n_slots, flags, buckets, stream
+_COMM = [ctypes.POINTER(_p), _i, _p, _i]
+# every function of include/rpkt_gpu.h: name -> (restype, argtypes)
+ABI = {
+    "rpkt_gpu_abi_version": (_u32, []),
+    "rpkt_gpu_build_info": (ctypes.c_char_p, []),
+    "rpkt_gpu_status_name": (ctypes.c_char_p, [_i]),
+    "rpkt_gpu_last_hip_error": (_i, []),
+    "rpkt_gpu_device_info": (_i, [ctypes.c_char_p, _sz]),
+    "rpkt_gpu_parse_batch": (_i, _PARSE),
+    "rpkt_gpu_parse_batch_compact": (_i, _PARSE),
+    "rpkt_gpu_parse_ring": (_i, [ctypes.POINTER(RingSlot)] + _RING),
+    "rpkt_gpu_parse_ring_compact": (_i, [ctypes.POINTER(RingSlot)] + _RING),
+    "rpkt_gpu_flow_workspace_bytes": (_sz, [_u32, _u32]),
+    "rpkt_gpu_flow_count": (_i, [_p, _u32, _u32, _p, _p, _p]),
+    "rpkt_gpu_checksum_ranges": (_i, [_p, ctypes.c_uint64, _p, _u32, _p, _p]),
+    "rpkt_gpu_checksum_chains_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_checksum_chains": (_i, [_p, ctypes.c_uint64, _p, _u32, _p, _u32, _p, _p, _p]),
+    "rpkt_gpu_parse_chains": (_i, [_C] + _PARSE[1:]),
+    "rpkt_gpu_build_batch": (_i, [_B, _p, _u32, _p, _p]),
+    "rpkt_gpu_build_tunnel_batch": (_i, [_B, _p, _p, _u32, _p, _p]),
+    "rpkt_gpu_forward_batch": (_i, [_B, ctypes.POINTER(Fwd), _p, _p]),
+    "rpkt_gpu_options_batch": (_i, [_B, _p, _p, _p]),
+    "rpkt_gpu_options_batch_compact": (_i, [_B, _p, _p, _p]),
+    "rpkt_gpu_parse_options_batch": (_i, [_B, _u32, _p, _p, _p, _u32, _p]),
+    "rpkt_gpu_parse_options_batch_compact": (_i, [_B, _u32, _p, _p, _p, _u32, _p]),
+    "rpkt_gpu_parse_tunnel_batch": (_i, [_B, _u32, _p, _p, _p, _p, _u32, _p]),
+    "rpkt_gpu_parse_tunnel_ring": (_i, [ctypes.POINTER(TunRingSlot)] + _RING),
+    "rpkt_gpu_parse_tunnel_chains": (_i, [_C, _u32, _p, _p, _p, _p, _u32, _p]),
+    "rpkt_gpu_parse_tunnel_next": (_i, [_B, _u32, _p, _p, _p, _p, _p, _u32, _p]),
+    "rpkt_gpu_layers_batch": (_i, [_B, _p, _p]),
+    "rpkt_gpu_fields_batch": (_i, [_B, _p, _p, _u32, _p, _p, _p]),
+    "rpkt_gpu_flow_reduce": (_i, [_p, _u32, _i, _p, _p]),
+    "rpkt_gpu_last_coll_error": (_i, []),
+    "rpkt_gpu_coll_version": (_i, []),
+    "rpkt_gpu_coll_unique_id": (_i, [_p]),
+    "rpkt_gpu_comm_init": (_i, _COMM),
+    "rpkt_gpu_comm_init_timeout": (_i, _COMM + [_i]),
+    "rpkt_gpu_comm_destroy": (_i, [_p]),
+    "rpkt_gpu_comm_abort": (_i, [_p]),
+    "rpkt_flow_hash": (_u32, [_u32, _u32, ctypes.c_uint16, ctypes.c_uint16, ctypes.c_uint8]),
+}
+EXPORTS = list(ABI)
 COLL_ID_BYTES = 128
 
 _lib = None
@@ -86,110 +118,9 @@ def lib():
             raise RpktError("HIP engine not built: %s missing (run __graft_entry__.build())"
                             % GPU_LIB)
         L = ctypes.CDLL(GPU_LIB)
-        L.rpkt_gpu_abi_version.restype = ctypes.c_uint32
-        L.rpkt_gpu_build_info.restype = ctypes.c_char_p
-        L.rpkt_gpu_status_name.argtypes = [ctypes.c_int]
-        L.rpkt_gpu_status_name.restype = ctypes.c_char_p
-        L.rpkt_gpu_last_hip_error.restype = ctypes.c_int
-        L.rpkt_gpu_device_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        L.rpkt_gpu_device_info.restype = ctypes.c_int
-        L.rpkt_gpu_parse_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_uint32,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                           ctypes.c_void_p]
-        L.rpkt_gpu_parse_batch.restype = ctypes.c_int
-        L.rpkt_gpu_parse_batch_compact.argtypes = L.rpkt_gpu_parse_batch.argtypes
-        L.rpkt_gpu_parse_batch_compact.restype = ctypes.c_int
-        L.rpkt_gpu_parse_ring.argtypes = [ctypes.POINTER(RingSlot), ctypes.c_uint32,
-                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
-        L.rpkt_gpu_parse_ring.restype = ctypes.c_int
-        L.rpkt_gpu_parse_ring_compact.argtypes = L.rpkt_gpu_parse_ring.argtypes
-        L.rpkt_gpu_parse_ring_compact.restype = ctypes.c_int
-        L.rpkt_gpu_flow_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-        L.rpkt_gpu_flow_workspace_bytes.restype = ctypes.c_size_t
-        L.rpkt_gpu_flow_count.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_flow_count.restype = ctypes.c_int
-        L.rpkt_gpu_checksum_ranges.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_checksum_ranges.restype = ctypes.c_int
-        L.rpkt_gpu_checksum_chains_workspace_bytes.argtypes = [ctypes.c_uint32]
-        L.rpkt_gpu_checksum_chains_workspace_bytes.restype = ctypes.c_size_t
-        L.rpkt_gpu_checksum_chains.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_checksum_chains.restype = ctypes.c_int
-        L.rpkt_gpu_parse_chains.argtypes = [ctypes.POINTER(Chains), ctypes.c_uint32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                            ctypes.c_void_p]
-        L.rpkt_gpu_parse_chains.restype = ctypes.c_int
-        L.rpkt_gpu_build_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p, ctypes.c_uint32,
-                                           ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_build_batch.restype = ctypes.c_int
-        L.rpkt_gpu_forward_batch.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Fwd),
-                                             ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_forward_batch.restype = ctypes.c_int
-        L.rpkt_gpu_options_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_options_batch.restype = ctypes.c_int
-        L.rpkt_gpu_options_batch_compact.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
-                                                     ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_options_batch_compact.restype = ctypes.c_int
-        L.rpkt_gpu_parse_options_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_uint32,
-                                                   ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_uint32,
-                                                   ctypes.c_void_p]
-        L.rpkt_gpu_parse_options_batch.restype = ctypes.c_int
-        L.rpkt_gpu_parse_options_batch_compact.argtypes = L.rpkt_gpu_parse_options_batch.argtypes
-        L.rpkt_gpu_parse_options_batch_compact.restype = ctypes.c_int
-        L.rpkt_gpu_parse_tunnel_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_uint32,
-                                                  ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_uint32, ctypes.c_void_p]
-        L.rpkt_gpu_parse_tunnel_batch.restype = ctypes.c_int
-        L.rpkt_gpu_parse_tunnel_ring.argtypes = [ctypes.POINTER(TunRingSlot), ctypes.c_uint32,
-                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
-        L.rpkt_gpu_parse_tunnel_ring.restype = ctypes.c_int
-        L.rpkt_gpu_parse_tunnel_chains.argtypes = [ctypes.POINTER(Chains), ctypes.c_uint32,
-                                                   ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_uint32, ctypes.c_void_p]
-        L.rpkt_gpu_parse_tunnel_chains.restype = ctypes.c_int
-        L.rpkt_gpu_parse_tunnel_next.argtypes = [ctypes.POINTER(Batch), ctypes.c_uint32,
-                                                 ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_uint32,
-                                                 ctypes.c_void_p]
-        L.rpkt_gpu_parse_tunnel_next.restype = ctypes.c_int
-        L.rpkt_gpu_build_tunnel_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_uint32,
-                                                  ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_build_tunnel_batch.restype = ctypes.c_int
-        L.rpkt_gpu_layers_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
-                                            ctypes.c_void_p]
-        L.rpkt_gpu_layers_batch.restype = ctypes.c_int
-        L.rpkt_gpu_fields_batch.argtypes = [ctypes.POINTER(Batch), ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_fields_batch.restype = ctypes.c_int
-        L.rpkt_gpu_flow_reduce.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int,
-                                           ctypes.c_void_p, ctypes.c_void_p]
-        L.rpkt_gpu_flow_reduce.restype = ctypes.c_int
-        L.rpkt_gpu_last_coll_error.restype = ctypes.c_int
-        L.rpkt_gpu_coll_version.restype = ctypes.c_int
-        L.rpkt_gpu_coll_unique_id.argtypes = [ctypes.c_void_p]
-        L.rpkt_gpu_coll_unique_id.restype = ctypes.c_int
-        L.rpkt_gpu_comm_init.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_int]
-        L.rpkt_gpu_comm_init.restype = ctypes.c_int
-        L.rpkt_gpu_comm_destroy.argtypes = [ctypes.c_void_p]
-        L.rpkt_gpu_comm_destroy.restype = ctypes.c_int
-        L.rpkt_gpu_comm_init_timeout.argtypes = L.rpkt_gpu_comm_init.argtypes + [ctypes.c_int]
-        L.rpkt_gpu_comm_init_timeout.restype = ctypes.c_int
-        L.rpkt_gpu_comm_abort.argtypes = [ctypes.c_void_p]
-        L.rpkt_gpu_comm_abort.restype = ctypes.c_int
-        L.rpkt_flow_hash.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint16,
-                                     ctypes.c_uint16, ctypes.c_uint8]
-        L.rpkt_flow_hash.restype = ctypes.c_uint32
+        for name, (restype, argtypes) in ABI.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -268,24 +199,57 @@ class DeviceBatch:
                      self.stride, self.frame_len, self.n, 0)
 
 
-def alloc_records(n, device="cuda"):
+def _call(name, *args):
+    """One call of the C ABI; RpktError unless it returns RPKT_OK."""
+    _check(getattr(lib(), name)(*args), name)
+
+
+def _bytes(n, per, device):
+    """A uint8 tensor of n * per bytes on `device`."""
     torch = _torch()
-    return torch.empty(n * REC_BYTES, dtype=torch.uint8, device=device)
+    return torch.empty(n * per, dtype=torch.uint8, device=device)
+
+
+def _events(flags, flow_ev, n, device):
+    """The flow-event tensor of a call: the caller's, or with RPKT_F_FLOW_EV a fresh one."""
+    if flags & F_FLOW_EV and flow_ev is None:
+        torch = _torch()
+        flow_ev = torch.empty(n, dtype=torch.int64, device=device)
+    return flow_ev
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def alloc_records(n, device="cuda"):
+    return _bytes(n, REC_BYTES, device)
 
 
 def parse_batch(batch, flags=3, recs=None, flow_ev=None, n_buckets=0, stream=None):
     """rpkt_gpu_parse_batch: returns the uint8 record tensor (n * 80 bytes)."""
-    torch = _torch()
-    if recs is None:
-        recs = alloc_records(batch.n, batch.frames.device)
-    if flags & F_FLOW_EV and flow_ev is None:
-        flow_ev = torch.empty(batch.n, dtype=torch.int64, device=batch.frames.device)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_parse_batch(ctypes.byref(d), flags, recs.data_ptr(),
-                                    flow_ev.data_ptr() if flow_ev is not None else None,
-                                    n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_batch")
+    return _parse("rpkt_gpu_parse_batch", batch, batch.frames.device, REC_BYTES, flags, recs,
+                  flow_ev, n_buckets, stream)
+
+
+def _parse(name, src, dev, rec_bytes, flags, recs, flow_ev, n_buckets, stream):
+    """parse_batch, parse_batch_compact and parse_chains: one record per frame of `src`."""
+    recs = _bytes(src.n, rec_bytes, dev) if recs is None else recs
+    flow_ev = _events(flags, flow_ev, src.n, dev)
+    _call(name, ctypes.byref(src.desc()), flags, recs.data_ptr(), _ptr(flow_ev), n_buckets,
+          _stream_ptr(stream))
     return (recs, flow_ev) if flags & F_FLOW_EV else recs
+
+
+def _parse_tunnel(name, src, dev, flags, outer, tun, inner, flow_ev, n_buckets, stream):
+    """parse_tunnel_batch and parse_tunnel_chains: three records per frame of `src`."""
+    outer = alloc_records(src.n, dev) if outer is None else outer
+    inner = alloc_records(src.n, dev) if inner is None else inner
+    tun = _bytes(src.n, 16, dev) if tun is None else tun
+    flow_ev = _events(flags, flow_ev, src.n, dev)
+    _call(name, ctypes.byref(src.desc()), flags, outer.data_ptr(), tun.data_ptr(),
+          inner.data_ptr(), _ptr(flow_ev), n_buckets, _stream_ptr(stream))
+    return (outer, tun, inner, flow_ev) if flags & F_FLOW_EV else (outer, tun, inner)
 
 
 def parse_tunnel_batch(batch, flags=3, outer=None, tun=None, inner=None, stream=None,
@@ -293,20 +257,8 @@ def parse_tunnel_batch(batch, flags=3, outer=None, tun=None, inner=None, stream=
     """rpkt_gpu_parse_tunnel_batch: returns (outer records, rpkt_tun_t, inner records) as
     uint8 tensors (n * 80, n * 16, n * 80 bytes); with RPKT_F_FLOW_EV also the flow events
     (int64 tensor of n: the inner record's event when the tunnel decoded, else the outer's)."""
-    torch = _torch()
-    dev = batch.frames.device
-    outer = alloc_records(batch.n, dev) if outer is None else outer
-    inner = alloc_records(batch.n, dev) if inner is None else inner
-    tun = torch.empty(batch.n * 16, dtype=torch.uint8, device=dev) if tun is None else tun
-    if flags & F_FLOW_EV and flow_ev is None:
-        flow_ev = torch.empty(batch.n, dtype=torch.int64, device=dev)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_parse_tunnel_batch(ctypes.byref(d), flags, outer.data_ptr(),
-                                           tun.data_ptr(), inner.data_ptr(),
-                                           flow_ev.data_ptr() if flow_ev is not None else None,
-                                           n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_tunnel_batch")
-    return (outer, tun, inner, flow_ev) if flags & F_FLOW_EV else (outer, tun, inner)
+    return _parse_tunnel("rpkt_gpu_parse_tunnel_batch", batch, batch.frames.device, flags, outer,
+                         tun, inner, flow_ev, n_buckets, stream)
 
 
 def parse_tunnel_next(batch, tun, inner, flags=3, tun_next=None, inner_next=None, flow_ev=None,
@@ -317,18 +269,12 @@ def parse_tunnel_next(batch, tun, inner, flags=3, tun_next=None, inner_next=None
     offset a position in the outermost frame.  With RPKT_F_FLOW_EV, flow_ev (required: the
     level before's events) gets the innermost record's event where the next tunnel decoded
     and keeps its other entries."""
-    torch = _torch()
     dev = batch.frames.device
-    if tun_next is None:
-        tun_next = torch.empty(batch.n * 16, dtype=torch.uint8, device=dev)
+    tun_next = _bytes(batch.n, 16, dev) if tun_next is None else tun_next
     inner_next = alloc_records(batch.n, dev) if inner_next is None else inner_next
-    d = batch.desc()
-    rc = lib().rpkt_gpu_parse_tunnel_next(ctypes.byref(d), flags, tun.data_ptr(),
-                                          inner.data_ptr(), tun_next.data_ptr(),
-                                          inner_next.data_ptr(),
-                                          flow_ev.data_ptr() if flow_ev is not None else None,
-                                          n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_tunnel_next")
+    _call("rpkt_gpu_parse_tunnel_next", ctypes.byref(batch.desc()), flags, tun.data_ptr(),
+          inner.data_ptr(), tun_next.data_ptr(), inner_next.data_ptr(), _ptr(flow_ev), n_buckets,
+          _stream_ptr(stream))
     return tun_next, inner_next
 
 
@@ -386,25 +332,14 @@ def tunnel_ring_slots(batches, outers, tuns, inners, flow_evs=None):
 def parse_tunnel_ring(slots, flags=3, n_buckets=0, stream=None):
     """rpkt_gpu_parse_tunnel_ring: every slot of `slots` (tunnel_ring_slots()) parsed as by
     parse_tunnel_batch, RPKT_RING_MAX_SLOTS slots per kernel launch."""
-    rc = lib().rpkt_gpu_parse_tunnel_ring(slots, len(slots), flags, n_buckets,
-                                          _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_tunnel_ring")
+    _call("rpkt_gpu_parse_tunnel_ring", slots, len(slots), flags, n_buckets, _stream_ptr(stream))
 
 
 def parse_batch_compact(batch, flags=3, recs=None, flow_ev=None, n_buckets=0, stream=None):
     """rpkt_gpu_parse_batch_compact: the same parse writing 16-byte rpkt_rec16_t
     records; returns the uint8 record tensor (n * 16 bytes)."""
-    torch = _torch()
-    if recs is None:
-        recs = torch.empty(batch.n * REC16_BYTES, dtype=torch.uint8, device=batch.frames.device)
-    if flags & F_FLOW_EV and flow_ev is None:
-        flow_ev = torch.empty(batch.n, dtype=torch.int64, device=batch.frames.device)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_parse_batch_compact(ctypes.byref(d), flags, recs.data_ptr(),
-                                            flow_ev.data_ptr() if flow_ev is not None else None,
-                                            n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_batch_compact")
-    return (recs, flow_ev) if flags & F_FLOW_EV else recs
+    return _parse("rpkt_gpu_parse_batch_compact", batch, batch.frames.device, REC16_BYTES, flags,
+                  recs, flow_ev, n_buckets, stream)
 
 
 def ring_slots(batches, recs, flow_evs=None, compact=None):
@@ -443,9 +378,8 @@ def parse_ring(slots, flags=3, n_buckets=0, stream=None, compact=False):
     RPKT_RING_MAX_SLOTS slots per kernel launch."""
     if not compact and getattr(slots, "_rpkt_compact_only", False):
         raise RpktError("parse_ring: some slot's records are sized for 16-B compact records")
-    fn = lib().rpkt_gpu_parse_ring_compact if compact else lib().rpkt_gpu_parse_ring
-    rc = fn(slots, len(slots), flags, n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_ring%s" % ("_compact" if compact else ""))
+    _call("rpkt_gpu_parse_ring_compact" if compact else "rpkt_gpu_parse_ring", slots, len(slots),
+          flags, n_buckets, _stream_ptr(stream))
 
 
 def flow_workspace(n, n_buckets, device="cuda"):
@@ -462,9 +396,8 @@ def flow_count(flow_ev, n, n_buckets, counters=None, workspace=None, stream=None
         counters = torch.zeros((n_buckets + 1) * 4, dtype=torch.int64, device=dev)
     if workspace is None:
         workspace = flow_workspace(n, n_buckets, dev)
-    rc = lib().rpkt_gpu_flow_count(flow_ev.data_ptr(), n, n_buckets, counters.data_ptr(),
-                                   workspace.data_ptr(), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_flow_count")
+    _call("rpkt_gpu_flow_count", flow_ev.data_ptr(), n, n_buckets, counters.data_ptr(),
+          workspace.data_ptr(), _stream_ptr(stream))
     return counters
 
 
@@ -474,9 +407,8 @@ def flow_reduce(counters, n_buckets, comm, root=-1, stream=None):
     nccl_comm_of()), in place; root -1 = all-reduce, else reduce to that rank."""
     if counters.numel() != (n_buckets + 1) * 4:
         raise RpktError("counters must hold (n_buckets + 1) * 4 words")
-    rc = lib().rpkt_gpu_flow_reduce(counters.data_ptr(), n_buckets, root,
-                                    ctypes.c_void_p(int(comm)), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_flow_reduce")
+    _call("rpkt_gpu_flow_reduce", counters.data_ptr(), n_buckets, root, ctypes.c_void_p(int(comm)),
+          _stream_ptr(stream))
     return counters
 
 
@@ -497,7 +429,7 @@ def nccl_comm_of(group=None):
 def coll_unique_id():
     """rpkt_gpu_coll_unique_id: a fresh RCCL unique id (bytes) for rpkt_gpu_comm_init."""
     buf = (ctypes.c_uint8 * COLL_ID_BYTES)()
-    _check(lib().rpkt_gpu_coll_unique_id(buf), "rpkt_gpu_coll_unique_id")
+    _call("rpkt_gpu_coll_unique_id", buf)
     return bytes(buf)
 
 
@@ -508,7 +440,7 @@ def comm_init(world, uid, rank):
         raise RpktError("comm_init: the id must be %d bytes" % COLL_ID_BYTES)
     buf = (ctypes.c_uint8 * COLL_ID_BYTES).from_buffer_copy(uid)
     comm = ctypes.c_void_p()
-    _check(lib().rpkt_gpu_comm_init(ctypes.byref(comm), world, buf, rank), "rpkt_gpu_comm_init")
+    _call("rpkt_gpu_comm_init", ctypes.byref(comm), world, buf, rank)
     return int(comm.value)
 
 
@@ -519,8 +451,7 @@ def comm_init_timeout(world, uid, rank, timeout_ms):
         raise RpktError("comm_init: the id must be %d bytes" % COLL_ID_BYTES)
     buf = (ctypes.c_uint8 * COLL_ID_BYTES).from_buffer_copy(uid)
     comm = ctypes.c_void_p()
-    rc = lib().rpkt_gpu_comm_init_timeout(ctypes.byref(comm), world, buf, rank, int(timeout_ms))
-    _check(rc, "rpkt_gpu_comm_init_timeout")
+    _call("rpkt_gpu_comm_init_timeout", ctypes.byref(comm), world, buf, rank, int(timeout_ms))
     return int(comm.value)
 
 
@@ -529,11 +460,11 @@ def last_coll_error():
 
 
 def comm_destroy(comm):
-    _check(lib().rpkt_gpu_comm_destroy(ctypes.c_void_p(int(comm))), "rpkt_gpu_comm_destroy")
+    _call("rpkt_gpu_comm_destroy", ctypes.c_void_p(int(comm)))
 
 
 def comm_abort(comm):
-    _check(lib().rpkt_gpu_comm_abort(ctypes.c_void_p(int(comm))), "rpkt_gpu_comm_abort")
+    _call("rpkt_gpu_comm_abort", ctypes.c_void_p(int(comm)))
 
 
 def checksum_ranges(buf, ranges, out=None, stream=None):
@@ -542,9 +473,8 @@ def checksum_ranges(buf, ranges, out=None, stream=None):
     n = ranges.numel() // 2
     if out is None:
         out = torch.empty(n, dtype=torch.int16, device=buf.device)
-    rc = lib().rpkt_gpu_checksum_ranges(buf.data_ptr(), buf.numel(), ranges.data_ptr(), n,
-                                        out.data_ptr(), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_checksum_ranges")
+    _call("rpkt_gpu_checksum_ranges", buf.data_ptr(), buf.numel(), ranges.data_ptr(), n,
+          out.data_ptr(), _stream_ptr(stream))
     return out
 
 
@@ -556,12 +486,9 @@ def checksum_chains(buf, segs, chain_first, out=None, stream=None):
     n_chains = chain_first.numel() - 1
     if out is None:
         out = torch.empty(max(n_chains, 0), dtype=torch.int16, device=buf.device)
-    ws = torch.empty(int(lib().rpkt_gpu_checksum_chains_workspace_bytes(n_segs)),
-                     dtype=torch.uint8, device=buf.device)
-    rc = lib().rpkt_gpu_checksum_chains(buf.data_ptr(), buf.numel(), segs.data_ptr(), n_segs,
-                                        chain_first.data_ptr(), n_chains, out.data_ptr(),
-                                        ws.data_ptr(), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_checksum_chains")
+    ws = _bytes(int(lib().rpkt_gpu_checksum_chains_workspace_bytes(n_segs)), 1, buf.device)
+    _call("rpkt_gpu_checksum_chains", buf.data_ptr(), buf.numel(), segs.data_ptr(), n_segs,
+          chain_first.data_ptr(), n_chains, out.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
     return out
 
 
@@ -594,17 +521,8 @@ class DeviceChains:
 
 def parse_chains(chains, flags=3, recs=None, flow_ev=None, n_buckets=0, stream=None):
     """rpkt_gpu_parse_chains: returns the uint8 record tensor (n * 80 bytes)."""
-    torch = _torch()
-    if recs is None:
-        recs = alloc_records(chains.n, chains.buf.device)
-    if flags & F_FLOW_EV and flow_ev is None:
-        flow_ev = torch.empty(chains.n, dtype=torch.int64, device=chains.buf.device)
-    d = chains.desc()
-    rc = lib().rpkt_gpu_parse_chains(ctypes.byref(d), flags, recs.data_ptr(),
-                                     flow_ev.data_ptr() if flow_ev is not None else None,
-                                     n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_chains")
-    return (recs, flow_ev) if flags & F_FLOW_EV else recs
+    return _parse("rpkt_gpu_parse_chains", chains, chains.buf.device, REC_BYTES, flags, recs,
+                  flow_ev, n_buckets, stream)
 
 
 def parse_tunnel_chains(chains, flags=3, outer=None, tun=None, inner=None, stream=None,
@@ -612,45 +530,25 @@ def parse_tunnel_chains(chains, flags=3, outer=None, tun=None, inner=None, strea
     """rpkt_gpu_parse_tunnel_chains: parse_tunnel_batch over mbuf chains.  Returns (outer
     records, rpkt_tun_t, inner records) as uint8 tensors (n * 80, n * 16, n * 80 bytes);
     with RPKT_F_FLOW_EV also the flow events (int64 tensor of n)."""
-    torch = _torch()
-    dev = chains.buf.device
-    outer = alloc_records(chains.n, dev) if outer is None else outer
-    inner = alloc_records(chains.n, dev) if inner is None else inner
-    tun = torch.empty(chains.n * 16, dtype=torch.uint8, device=dev) if tun is None else tun
-    if flags & F_FLOW_EV and flow_ev is None:
-        flow_ev = torch.empty(chains.n, dtype=torch.int64, device=dev)
-    d = chains.desc()
-    rc = lib().rpkt_gpu_parse_tunnel_chains(ctypes.byref(d), flags, outer.data_ptr(),
-                                            tun.data_ptr(), inner.data_ptr(),
-                                            flow_ev.data_ptr() if flow_ev is not None else None,
-                                            n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_tunnel_chains")
-    return (outer, tun, inner, flow_ev) if flags & F_FLOW_EV else (outer, tun, inner)
+    return _parse_tunnel("rpkt_gpu_parse_tunnel_chains", chains, chains.buf.device, flags, outer,
+                         tun, inner, flow_ev, n_buckets, stream)
 
 
 def build_batch(batch, recs, flags=3, built=None, stream=None):
     """rpkt_gpu_build_batch: write each frame's headers from its record, in place in
     batch.frames (payload already there).  Returns the per-frame built flags (u8)."""
-    torch = _torch()
-    if built is None:
-        built = torch.empty(batch.n, dtype=torch.uint8, device=batch.frames.device)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_build_batch(ctypes.byref(d), recs.data_ptr(), flags, built.data_ptr(),
-                                    _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_build_batch")
+    built = _bytes(batch.n, 1, batch.frames.device) if built is None else built
+    _call("rpkt_gpu_build_batch", ctypes.byref(batch.desc()), recs.data_ptr(), flags,
+          built.data_ptr(), _stream_ptr(stream))
     return built
 
 
 def build_tunnel_batch(batch, recs, tun, flags=3, built=None, stream=None):
     """rpkt_gpu_build_tunnel_batch: the outer headers of recs plus each frame's tunnel
     header of tun (uint8 tensors of n * 80 / n * 16 bytes); returns the built flags."""
-    torch = _torch()
-    if built is None:
-        built = torch.empty(batch.n, dtype=torch.uint8, device=batch.frames.device)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_build_tunnel_batch(ctypes.byref(d), recs.data_ptr(), tun.data_ptr(),
-                                           flags, built.data_ptr(), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_build_tunnel_batch")
+    built = _bytes(batch.n, 1, batch.frames.device) if built is None else built
+    _call("rpkt_gpu_build_tunnel_batch", ctypes.byref(batch.desc()), recs.data_ptr(),
+          tun.data_ptr(), flags, built.data_ptr(), _stream_ptr(stream))
     return built
 
 
@@ -667,8 +565,7 @@ def forward_batch(batch, dmac, smac, forbid=None, keep=None, stream=None, flags=
     forbid: None or a tensor from forbid_list(); flags: 0 or RPKT_F_IPV6 (8), which also
     forwards untagged IPv6/UDP frames."""
     torch = _torch()
-    if keep is None:
-        keep = torch.empty(batch.n, dtype=torch.uint8, device=batch.frames.device)
+    keep = _bytes(batch.n, 1, batch.frames.device) if keep is None else keep
     f = Fwd()
     f.dmac[:] = list(bytes(dmac))
     f.smac[:] = list(bytes(smac))
@@ -677,10 +574,8 @@ def forward_batch(batch, dmac, smac, forbid=None, keep=None, stream=None, flags=
         if forbid.dtype != torch.int32:
             raise RpktError("forbid must come from forbid_list() (sorted u32 as int32)")
         f.forbid_dev, f.n_forbid = forbid.data_ptr(), forbid.numel()
-    d = batch.desc()
-    rc = lib().rpkt_gpu_forward_batch(ctypes.byref(d), ctypes.byref(f), keep.data_ptr(),
-                                      _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_forward_batch")
+    _call("rpkt_gpu_forward_batch", ctypes.byref(batch.desc()), ctypes.byref(f), keep.data_ptr(),
+          _stream_ptr(stream))
     return keep
 
 
@@ -688,15 +583,12 @@ def options_batch(batch, recs, opts=None, stream=None, compact=False):
     """rpkt_gpu_options_batch: IPv4 and TCP option walks of a parsed batch
     (recs from parse_batch, or from parse_batch_compact with compact=True:
     rpkt_gpu_options_batch_compact); returns the uint8 tensor of n * 64-byte rpkt_opts_t."""
-    torch = _torch()
+    _torch()                                   # no GPU: RpktError before the size check
     if recs.numel() != batch.n * (REC16_BYTES if compact else REC_BYTES):
         raise RpktError("records: %d bytes for %d frames" % (recs.numel(), batch.n))
-    if opts is None:
-        opts = torch.empty(batch.n * OPTS_BYTES, dtype=torch.uint8, device=batch.frames.device)
-    d = batch.desc()
-    fn = lib().rpkt_gpu_options_batch_compact if compact else lib().rpkt_gpu_options_batch
-    rc = fn(ctypes.byref(d), recs.data_ptr(), opts.data_ptr(), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_options_batch_compact" if compact else "rpkt_gpu_options_batch")
+    opts = _bytes(batch.n, OPTS_BYTES, batch.frames.device) if opts is None else opts
+    _call("rpkt_gpu_options_batch_compact" if compact else "rpkt_gpu_options_batch",
+          ctypes.byref(batch.desc()), recs.data_ptr(), opts.data_ptr(), _stream_ptr(stream))
     return opts
 
 
@@ -705,33 +597,22 @@ def parse_options_batch(batch, flags=3, recs=None, opts=None, flow_ev=None, n_bu
     """rpkt_gpu_parse_options_batch[_compact]: the parse and both option walks in one
     pass.  Returns (records, opts) -- n * 80 (or 16, compact) and n * 64 bytes, uint8 --
     plus the flow events when RPKT_F_FLOW_EV is set."""
-    torch = _torch()
     dev = batch.frames.device
     if recs is None:
-        recs = torch.empty(batch.n * (REC16_BYTES if compact else REC_BYTES), dtype=torch.uint8,
-                           device=dev)
-    if opts is None:
-        opts = torch.empty(batch.n * OPTS_BYTES, dtype=torch.uint8, device=dev)
-    if flags & F_FLOW_EV and flow_ev is None:
-        flow_ev = torch.empty(batch.n, dtype=torch.int64, device=dev)
-    d = batch.desc()
-    fn = (lib().rpkt_gpu_parse_options_batch_compact if compact
-          else lib().rpkt_gpu_parse_options_batch)
-    rc = fn(ctypes.byref(d), flags, recs.data_ptr(), opts.data_ptr(),
-            flow_ev.data_ptr() if flow_ev is not None else None, n_buckets, _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_parse_options_batch%s" % ("_compact" if compact else ""))
+        recs = _bytes(batch.n, REC16_BYTES if compact else REC_BYTES, dev)
+    opts = _bytes(batch.n, OPTS_BYTES, dev) if opts is None else opts
+    flow_ev = _events(flags, flow_ev, batch.n, dev)
+    _call("rpkt_gpu_parse_options_batch_compact" if compact else "rpkt_gpu_parse_options_batch",
+          ctypes.byref(batch.desc()), flags, recs.data_ptr(), opts.data_ptr(), _ptr(flow_ev),
+          n_buckets, _stream_ptr(stream))
     return (recs, opts, flow_ev) if flags & F_FLOW_EV else (recs, opts)
 
 
 def layers_batch(batch, out=None, stream=None):
     """rpkt_gpu_layers_batch: the protocol stack of every frame (pktfmt-derived
     walk); returns the uint8 tensor of n * 64-byte rpkt_layers_t."""
-    torch = _torch()
-    if out is None:
-        out = torch.empty(batch.n * LAYERS_BYTES, dtype=torch.uint8, device=batch.frames.device)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_layers_batch(ctypes.byref(d), out.data_ptr(), _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_layers_batch")
+    out = _bytes(batch.n, LAYERS_BYTES, batch.frames.device) if out is None else out
+    _call("rpkt_gpu_layers_batch", ctypes.byref(batch.desc()), out.data_ptr(), _stream_ptr(stream))
     return out
 
 
@@ -751,10 +632,7 @@ def fields_batch(batch, layers, reqs, values=None, present=None, stream=None):
         values = torch.empty((batch.n, k), dtype=torch.int64, device=dev)   # u64 bits
     if present is None:
         present = torch.empty(batch.n, dtype=torch.int32, device=dev)
-    d = batch.desc()
-    rc = lib().rpkt_gpu_fields_batch(ctypes.byref(d), layers.data_ptr(),
-                                     reqs.ctypes.data_as(ctypes.c_void_p), k,
-                                     values.data_ptr(), present.data_ptr(),
-                                     _stream_ptr(stream))
-    _check(rc, "rpkt_gpu_fields_batch")
+    _call("rpkt_gpu_fields_batch", ctypes.byref(batch.desc()), layers.data_ptr(),
+          reqs.ctypes.data_as(ctypes.c_void_p), k, values.data_ptr(), present.data_ptr(),
+          _stream_ptr(stream))
     return values, present
