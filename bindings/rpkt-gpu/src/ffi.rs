@@ -378,6 +378,16 @@ extern "C" {
                                       inner_next_dev: *mut rpkt_rec_t,
                                       flow_ev_dev: *mut rpkt_flow_ev_t, n_buckets: u32,
                                       stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_segment_batch for n input frames.
+    pub fn rpkt_gpu_segment_workspace_bytes(n: u32) -> usize;
+    /// TCP segmentation (TSO) on the device: each TCP frame whose payload exceeds `mss` is cut
+    /// into MSS-sized segments with fixed-up headers and fresh checksums, every other frame
+    /// copied; the output is a packed batch of `out_cap` slots.
+    pub fn rpkt_gpu_segment_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
+                                  mss: u32, flags: u32, out_frames_dev: *mut u8, out_bytes: u64,
+                                  out_offsets_dev: *mut u32, out_cap: u32,
+                                  seg_first_dev: *mut u32, totals_dev: *mut u64,
+                                  workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn rpkt_gpu_build_tunnel_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
                                        tun_dev: *const rpkt_tun_t, flags: u32, built_dev: *mut u8,
                                        stream: *mut c_void) -> c_int;

@@ -412,6 +412,39 @@ pub unsafe fn parse_tunnel_chains(chains: &ffi::rpkt_chains_t, flags: u32, outer
                                             core::ptr::null_mut(), 0, stream))
 }
 
+/// The outputs of rpkt_gpu_segment_batch: a packed batch of `out_cap` slots (`frames_dev`,
+/// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first output
+/// of every input frame (`seg_first_dev`, `n + 1` entries) and `totals_dev` (u64[2], 8-byte
+/// aligned: the output frame count and the output bytes needed).
+pub struct SegmentOut {
+    pub frames_dev: *mut u8,
+    pub out_bytes: u64,
+    pub offsets_dev: *mut u32,
+    pub out_cap: u32,
+    pub seg_first_dev: *mut u32,
+    pub totals_dev: *mut u64,
+}
+
+/// rpkt_gpu_segment_workspace_bytes: the workspace of segment_batch for `n` input frames.
+pub fn segment_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_segment_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_segment_batch: TCP segmentation (TSO) of a parsed batch at `mss` (1..65535).
+///
+/// # Safety
+/// `batch` must describe device memory valid for the call; `recs_dev` must be the records a
+/// parse wrote for this same batch; every pointer of `out` must be device memory of the size
+/// its field documents, and `workspace_dev` must hold `segment_workspace_bytes(batch.n)`
+/// bytes (16-byte aligned), all on the same device.
+pub unsafe fn segment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mss: u32,
+                            out: &SegmentOut, workspace_dev: *mut core::ffi::c_void,
+                            stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_segment_batch(batch, recs_dev, mss, 0, out.frames_dev, out.out_bytes,
+                                      out.offsets_dev, out.out_cap, out.seg_first_dev,
+                                      out.totals_dev, workspace_dev, stream))
+}
+
 /// rpkt_gpu_parse_tunnel_next: the next tunnel level (nested tunnels) from the tunnel and
 /// inner records of the level before, without flow events.
 ///

@@ -99,7 +99,13 @@ enum rpkt_status {
  *   tunnel entries (batch, chains, next, ring): only the descriptor is tested before the
  *     flags and n == 0, the record pointers after it with frames_dev;
  *   ring entries: NULL slots with n_slots > 0, the flags, then each non-empty slot in
- *     order with its batch entry's checks, all before the first launch.
+ *     order with its batch entry's checks, all before the first launch;
+ *   rpkt_gpu_segment_batch: the batch entries' order with its own arguments in their places:
+ *     a NULL batch, recs_dev, output (out_frames_dev, out_offsets_dev, seg_first_dev,
+ *     totals_dev) or workspace_dev (E_INVAL); flags other than 0, then mss outside 1..65535
+ *     (E_INVAL); n == 0 (RPKT_OK); NULL frames_dev (E_INVAL); frames_bytes, then out_bytes at
+ *     the same limit (E_TOO_LARGE); no layout (E_INVAL); out_cap == 0 (E_INVAL); alignment
+ *     (E_ALIGN): recs_dev, out_frames_dev, workspace_dev 16 B, totals_dev 8 B.
  * Where an entry leaves that order (kept as it is, callers may rely on it):
  *   rpkt_gpu_parse_tunnel_batch and each slot of rpkt_gpu_parse_tunnel_ring test the flow
  *     events first, before n == 0: an empty batch with RPKT_F_FLOW_EV and no event buffer is
@@ -689,6 +695,69 @@ typedef struct rpkt_fwd {
 } rpkt_fwd_t;
 int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uint8_t* keep_dev,
                            void* stream);
+
+/* ---- TCP segmentation (TSO) ---------------------------------------------------- */
+
+/* The third TX offload of the reference's examples: rpkt-dpdk/examples/tso_tx.rs:128-134
+ * sets TCP_SEG (1 << 50) next to the IP_CKSUM / TCP_CKSUM bits, l2_len / l3_len / l4_len and
+ * set_tso_segsz(1024), and the port cuts the 4000-byte frame into MSS-sized TCP segments
+ * with fixed-up headers and fresh checksums.  rpkt_gpu_segment_batch does that cut on the
+ * device, for frames that stay in HBM, under the Linux tcp_gso_segment / DPDK rte_gso TCP
+ * rules.  The output is the complete transmit batch, in input order: every input frame
+ * yields one output frame or more.
+ *
+ * recs_dev: the rpkt_rec_t records of a parse of this same batch (RPKT_F_IPV6 for IPv6
+ * frames; the sum flags do not matter).  As for rpkt_gpu_options_batch the records only
+ * locate things -- status, the dispatch ethertype, ip_protocol, ip_frag, l3_off, l4_off,
+ * payload_off, payload_len, ip6_pdst_off -- and every header byte is taken from the frame.
+ * mss: 1..65535.  flags: 0 (reserved for UDP segmentation).
+ *
+ * Frame i is segmented iff status == RPKT_S_OK, ip_protocol == 6, for IPv4
+ * (ip_frag & 0x3fff) == 0 (not a fragment) and payload_len > mss; it yields
+ * n_i = ceil(payload_len / mss) frames.  Every other frame (UDP, unparsed, short TCP,
+ * fragments) passes through as one frame, a byte copy of [0, frame_len).
+ * Segment k of a segmented frame, with p_k = mss but p_last = payload_len - (n_i - 1) * mss:
+ *   bytes   [0, payload_off) of the frame (Ethernet, tags, the IP header with its options or
+ *           extension headers, the TCP header with its options: any length), then payload
+ *           bytes [payload_off + k * mss, + p_k); bytes after the IP packet's end (Ethernet
+ *           padding) are not carried;
+ *   IPv4    packet_len = (payload_off - l3_off) + p_k; ident = (ident + k) & 0xffff; the
+ *           header checksum filled as RPKT_BUILD_IP_CSUM fills it;
+ *   IPv6    payload_len = (payload_off - l3_off - 40) + p_k; extension headers untouched;
+ *   TCP     seq = seq + k * mss (mod 2^32); FIN (0x01) and PSH (0x08) cleared on every
+ *           segment but the last, CWR (0x80) on every segment but the first; everything
+ *           else, options included, copied; the checksum filled as RPKT_BUILD_L4_CSUM fills
+ *           a TCP one, over the pseudo header (for IPv6 its destination is the address at
+ *           ip6_pdst_off under rpkt_gpu_build_batch's rule), the header and the segment's
+ *           payload; a result of 0 stays 0.
+ *
+ * Outputs:
+ *   seg_first_dev  n + 1 entries: the outputs of frame i are [seg_first[i], seg_first[i+1]);
+ *   totals_dev     u64[2], 8-byte aligned: {n_out, out_bytes_needed}, whatever the capacities;
+ *   out_frames_dev (16-byte aligned, out_bytes bytes) and out_offsets_dev (out_cap + 1
+ *                  entries): a packed rpkt_batch_t.  When n_out <= out_cap and
+ *                  out_bytes_needed <= out_bytes, entries 0..n_out are the true offsets
+ *                  (frames back to back from 0, no padding) and entries n_out+1..out_cap
+ *                  equal out_bytes_needed: a parse over all out_cap slots needs no host round
+ *                  trip, the spare slots are empty frames.  Otherwise (overflow) seg_first_dev
+ *                  and totals_dev are still exact and the rest is unspecified; nothing is ever
+ *                  written outside [out_frames_dev, + out_bytes) and out_offsets_dev[0..out_cap].
+ * Bounds for sizing: n_out <= n + floor(frames_bytes / mss); out_bytes_needed <= frames_bytes
+ * + (n_out - n) * H, H the longest header (payload_off) of the batch.  (n_out > 2^32 - 1
+ * does not fit seg_first_dev; out_cap cannot hold it either.)
+ * workspace_dev: rpkt_gpu_segment_workspace_bytes(n) bytes, 16-byte aligned; calls that
+ * share one must be ordered (one stream).  The call is plan, prefix sums and write on
+ * `stream` with no host step, so it can be captured in a graph with the parse that follows.
+ * The records must come from a parse of the same batch.  With other records the outputs are
+ * unspecified, but every frame byte is read through the bounds-checked buffer resource with
+ * [payload_off, + payload_len) clamped to the frame's span, and a record whose offsets do not
+ * nest as a parse leaves them (l3_off + 20 (IPv6: 40) <= l4_off, l4_off + 20 <= payload_off
+ * <= frame_len, header lengths within 60) passes through: wrong frames, never a fault. */
+size_t rpkt_gpu_segment_workspace_bytes(uint32_t n);
+int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev, uint32_t mss,
+                           uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
+                           uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
+                           uint64_t* totals_dev, void* workspace_dev, void* stream);
 
 /* ---- Option iterators ----------------------------------------------------------- */
 

@@ -1,0 +1,550 @@
+// rpkt_segment.hip — rpkt_gpu_segment_batch: TCP segmentation (TSO) of a device-resident
+// batch, the TCP_SEG transmit offload of rpkt-dpdk/examples/tso_tx.rs:128-134 under the
+// Linux tcp_gso_segment / DPDK rte_gso rules (include/rpkt_gpu.h has the semantics).
+//
+// The output batch has another frame count and other offsets than the input, so the work
+// is planned from the input and split by the output.  Four launches on the stream, no host
+// step between them:
+//   1. plan   one lane per input frame: its record (coalesced through an LDS stage) says
+//             whether it is segmented; n_i outputs and their bytes go to seg_first / the
+//             workspace, with the block's sums, and for a segmented frame the constants
+//             every one of its segments shares (the IPv4 header sum without packet_len /
+//             ident / checksum, the TCP header + pseudo header sum without seq / flags /
+//             checksum / length), read from the frame once per super-frame;
+//   2. scan   exclusive prefix sums of counts and bytes: one block over the block sums
+//             (with a carry from each 256 to the next), then one block per 256 frames;
+//   3. write  one wavefront per run of kSegRun consecutive OUTPUT frames: it finds the first
+//             one's input frame by a 64-way search of seg_first and steps along seg_first
+//             for the others.  Per output it copies the payload slice in 16-B chunks of the
+//             destination (source and destination at any two byte phases: two aligned 16-B
+//             loads and a byte funnel shift per chunk), sums the bytes it copies (absolute
+//             destination phase, be_sum), and then writes the header with the patched fields
+//             and the two checksums.  A pass-through frame is the same copy without the sum.
+// Every load goes through the frames buffer resource and every store through one over
+// [out_frames_dev, + out_bytes); an overflowing batch (totals past the capacities) writes
+// its totals and seg_first and nothing else.
+#include "rpkt_common.h"
+#include "rpkt_args.h"
+
+namespace {
+
+constexpr int kSegBlock = kWave * kWavesPerBlock;   // frames per block in plan and scan
+
+// the workspace: per-frame plans (32 B), per-frame output byte bases (u64), block sums
+// (count, bytes: u64 pairs)
+struct SegWs {
+    u32x4*    plan;
+    uint64_t* obase;
+    uint64_t* part;
+};
+inline uint32_t seg_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSegBlock - 1) / kSegBlock); }
+inline size_t seg_ws_bytes(uint32_t n) {
+    return (size_t)n * 32u + (((size_t)n * 8u + 15u) & ~(size_t)15u) + (size_t)seg_blocks(n) * 16u;
+}
+inline SegWs seg_ws(void* ws, uint32_t n) {
+    uint8_t* p = static_cast<uint8_t*>(ws);
+    SegWs w;
+    w.plan = reinterpret_cast<u32x4*>(p);
+    w.obase = reinterpret_cast<uint64_t*>(p + (size_t)n * 32u);
+    w.part = reinterpret_cast<uint64_t*>(p + (size_t)n * 32u + (((size_t)n * 8u + 15u) & ~(size_t)15u));
+    return w;
+}
+
+// plan words: 0 frame offset, 1 frame length, 2 l3 | l4 << 16, 3 payload_off | payload_len
+// << 16, 4 IPv4 constant sum | ident << 16, 5 TCP constant sum | be16 of TCP bytes 12..13
+// << 16, 6 seq, 7 bit 0 segmented, bit 1 IPv6
+constexpr uint32_t kSegOn = 1u, kSegV6 = 2u;
+
+// the aligned dword at x (bytes past the buffer read as 0: its last, partial dword by bytes)
+__device__ __forceinline__ uint32_t ldw(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t x) {
+    if (__builtin_expect(x + 4u <= fb, 1))
+        return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)x, 0, 0);
+    return gbyte(rs, x) | (gbyte(rs, x + 1u) << 8) | (gbyte(rs, x + 2u) << 16) |
+           (gbyte(rs, x + 3u) << 24);
+}
+
+// big-endian RFC 1071 sum (folded) of buffer bytes [a, b), one lane: headers, addresses
+__device__ __forceinline__ uint32_t range_be_sum(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 uint32_t a, uint32_t b) {
+    if (b <= a) return 0u;
+    uint32_t acc = 0;
+    for (uint32_t x = a & ~3u; x < b; x += 4u) {
+        const uint32_t lo = a > x ? a - x : 0u, hi = b - x < 4u ? b - x : 4u;
+        acc = hsum(ldw(rs, fb, x) & byte_mask((int)lo, (int)hi), acc);
+    }
+    return be_sum(acc, a);
+}
+
+// 64-bit inclusive scan over the wave
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x, int lane) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint64_t y = __shfl_up((unsigned long long)x, d, kWave);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+
+// Exclusive scan of (a, b) over the block's kSegBlock threads; tot_*: the block's sums.
+// red: 4 * kWavesPerBlock u64 of LDS.
+__device__ __forceinline__ void block_excl_scan2(uint64_t& a, uint64_t& b, uint64_t& tot_a,
+                                                 uint64_t& tot_b, uint64_t* red) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint64_t ia = wave_incl_scan64(a, lane), ib = wave_incl_scan64(b, lane);
+    if (lane == kWave - 1) {
+        red[2 * wave] = ia;
+        red[2 * wave + 1] = ib;
+    }
+    __syncthreads();
+    uint64_t ba = 0, bb = 0;
+    tot_a = tot_b = 0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) {
+        if (w < wave) {
+            ba += red[2 * w];
+            bb += red[2 * w + 1];
+        }
+        tot_a += red[2 * w];
+        tot_b += red[2 * w + 1];
+    }
+    __syncthreads();                                   // red is free for the next call
+    a = ba + ia - a;
+    b = bb + ib - b;
+}
+
+// ---- 1. plan ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kSegBlock)
+void segment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
+                         const uint32_t* __restrict__ offsets, uint32_t stride, uint32_t frame_len,
+                         uint32_t n, const rpkt_rec_t* __restrict__ recs, uint32_t mss,
+                         u32x4* __restrict__ plan, uint32_t* __restrict__ seg_first,
+                         uint64_t* __restrict__ obase, uint64_t* __restrict__ part) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    uint64_t cnt = 0, bytes = 0;
+
+    if (p0 < n) {                                                 // wave-uniform
+        // the tile's records, coalesced: 5 dwordx4 per lane over its contiguous 5 KiB into
+        // the stage (stride 21 dwords), as rpkt_tx.hip's load_records_tile
+        uint32_t* st = stage[wave];
+        {
+            const uint32_t nrec = n - p0 < (uint32_t)kWave ? n - p0 : (uint32_t)kWave;
+            const u32x4* in = reinterpret_cast<const u32x4*>(recs + p0);
+            u32x4 v[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const uint32_t c = k * kWave + lane;
+                v[k] = c / 5 < nrec ? __builtin_nontemporal_load(&in[c]) : u32x4{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const uint32_t c = k * kWave + lane;
+                uint32_t* d = st + (c / 5) * 21 + (c % 5) * 4;
+                d[0] = v[k].x;
+                d[1] = v[k].y;
+                d[2] = v[k].z;
+                d[3] = v[k].w;
+            }
+            wave_sync();
+        }
+        const uint32_t* w = st + lane * 21;
+        const uint32_t w0 = w[0], w5 = w[5], w7 = w[7], w8 = w[8], w16 = w[16], w17 = w[17];
+        const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
+        const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
+        const bool v6 = det == 0x86ddu;
+        const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
+        const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
+
+        const Frame fr = valid ? frame_span(offsets, stride, frame_len, fb, i) : Frame{0u, 0u};
+        // offsets that nest as a parse of this frame leaves them; [po, + pl) inside the frame
+        const bool nest = l4 >= l3 && po >= l4 && po <= fr.len && po - l4 >= 20u &&
+                          po - l4 <= 60u &&
+                          (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
+        uint32_t pl = w17 >> 16;
+        if (nest && pl > fr.len - po) pl = fr.len - po;
+        const bool seg = valid && status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
+                         (v6 || (frag & 0x3fffu) == 0u) && nest && pl > mss;
+        uint32_t p[8] = {fr.off, fr.len, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (valid) {
+            cnt = 1;
+            bytes = fr.len;
+        }
+        if (seg) {
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+            const uint32_t a3 = fr.off + l3, a4 = fr.off + l4;
+            cnt = (pl + mss - 1u) / mss;
+            bytes = cnt * po + pl;
+            // a field leaves a sum by adding its complement (one's complement arithmetic;
+            // the sums stay positive, so the folded values are the plain sums')
+            uint32_t ipc = 0, pseudo;
+            const uint32_t ip0 = gdword(rs, fb, a3);
+            uint32_t ident = 0;
+            if (!v6) {
+                const uint32_t ip1 = gdword(rs, fb, a3 + 4u), ip2 = gdword(rs, fb, a3 + 8u);
+                ident = be16_lo(ip1);
+                ipc = range_be_sum(rs, fb, a3, a4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ ident) +
+                      (0xffffu ^ be16_hi(ip2));
+                pseudo = range_be_sum(rs, fb, a3 + 12u, a3 + 20u);
+            } else {
+                // the pseudo destination: rpkt_gpu_build_batch's rule
+                const uint32_t pd = (pdst >= l3 + 24u && pdst + 16u <= l4) ? pdst : l3 + 24u;
+                pseudo = range_be_sum(rs, fb, a3 + 8u, a3 + 24u) +
+                         range_be_sum(rs, fb, fr.off + pd, fr.off + pd + 16u);
+            }
+            const uint32_t t1 = gdword(rs, fb, a4 + 4u), t3 = gdword(rs, fb, a4 + 12u);
+            const uint32_t t4 = gdword(rs, fb, a4 + 16u);
+            const uint32_t seq = bswap32(t1), w12 = be16_lo(t3);
+            const uint32_t tcpc = range_be_sum(rs, fb, a4, fr.off + po) + pseudo + 6u +
+                                  (0xffffu ^ (seq >> 16)) + (0xffffu ^ (seq & 0xffffu)) +
+                                  (0xffffu ^ w12) + (0xffffu ^ be16_lo(t4));
+            p[2] = l3 | (l4 << 16);
+            p[3] = po | (pl << 16);
+            p[4] = fold16(ipc) | (ident << 16);
+            p[5] = fold16(tcpc) | (w12 << 16);
+            p[6] = seq;
+            p[7] = kSegOn | (v6 ? kSegV6 : 0u);
+        }
+        if (valid) {
+            plan[2 * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
+            plan[2 * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
+            seg_first[i] = (uint32_t)cnt;
+            obase[i] = bytes;
+        }
+    }
+    uint64_t tc, tb;
+    block_excl_scan2(cnt, bytes, tc, tb, red);
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)blockIdx.x] = tc;
+        part[2 * (size_t)blockIdx.x + 1] = tb;
+    }
+}
+
+// ---- 2. scan ---------------------------------------------------------------------------
+
+// one block: the block sums -> their exclusive prefixes, kSegBlock at a time with a carry;
+// the totals
+__global__ __launch_bounds__(kSegBlock)
+void segment_scan_parts_kernel(uint64_t* __restrict__ part, uint32_t nb, uint32_t n,
+                               uint32_t* __restrict__ seg_first, uint64_t* __restrict__ totals) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    uint64_t ca = 0, cb = 0;
+    for (uint32_t base = 0; base < nb; base += kSegBlock) {
+        const uint32_t k = base + threadIdx.x;
+        uint64_t a = k < nb ? part[2 * (size_t)k] : 0, b = k < nb ? part[2 * (size_t)k + 1] : 0;
+        uint64_t ta, tb;
+        block_excl_scan2(a, b, ta, tb, red);
+        if (k < nb) {
+            part[2 * (size_t)k] = ca + a;
+            part[2 * (size_t)k + 1] = cb + b;
+        }
+        ca += ta;
+        cb += tb;
+    }
+    if (threadIdx.x == 0) {
+        totals[0] = ca;
+        totals[1] = cb;
+        seg_first[n] = (uint32_t)ca;
+    }
+}
+
+// one block per kSegBlock frames: counts and bytes -> seg_first and the output byte bases
+__global__ __launch_bounds__(kSegBlock)
+void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
+                                uint32_t* __restrict__ seg_first, uint64_t* __restrict__ obase) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
+    uint64_t a = i < n ? seg_first[i] : 0, b = i < n ? obase[i] : 0;
+    uint64_t ta, tb;
+    block_excl_scan2(a, b, ta, tb, red);
+    if (i < n) {
+        seg_first[i] = (uint32_t)(part[2 * (size_t)blockIdx.x] + a);
+        obase[i] = part[2 * (size_t)blockIdx.x + 1] + b;
+    }
+}
+
+// ---- 3. write --------------------------------------------------------------------------
+
+// bytes [lo, hi) of dword v to the output at x (4-B aligned): one dword store, or bytes
+__device__ __forceinline__ void store_dword_part(__amdgpu_buffer_rsrc_t ro, uint32_t x, uint32_t v,
+                                                 int lo, int hi) {
+    if (hi <= 0 || lo >= 4) return;
+    if (lo <= 0 && hi >= 4) {
+        __builtin_amdgcn_raw_buffer_store_b32(v, ro, (int)x, 0, 0);
+        return;
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (b >= lo && b < hi)
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(v >> (8 * b)), ro, (int)(x + b), 0, 0);
+}
+
+// Copy src [s0, s0 + len) of the frames buffer to dst [d0, d0 + len) of the output, the
+// whole wave: lane l of pass t owns the 16-B aligned destination chunk t * 64 + l.  The
+// chunk's source bytes start at phase sh = (s0 - d0) & 15 of an aligned source chunk
+// (wave-uniform), so they are that chunk and the next, shifted.  Whole chunks go out as one
+// dwordx4 store, the (at most two) partial ones as dwords and bytes: their other bytes belong
+// to the neighbouring output frames, which other waves write.  Returns this lane's part of
+// the word sum of the bytes copied, over absolute-destination-aligned LE words (SUM).
+constexpr int kCopyUnroll = 2;     // destination chunks (and their loads) in flight per lane
+#ifndef RPKT_SEG_NT
+#define RPKT_SEG_NT 0              // 2: non-temporal copy loads and dwordx4 stores
+#endif
+constexpr int kCopyAux = RPKT_SEG_NT;
+template <bool SUM>
+__device__ __forceinline__ uint32_t wave_copy(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                              __amdgpu_buffer_rsrc_t ro, uint32_t s0, uint32_t d0,
+                                              uint32_t len, int lane) {
+    uint32_t acc = 0;
+    if (len == 0) return acc;
+    const uint32_t dbase = d0 & ~15u, dend = d0 + len;
+    const uint32_t sh = (s0 - d0) & 15u, q = sh >> 2, r = sh & 3u;       // wave-uniform
+    const uint32_t nchunk = (dend - dbase + 15u) >> 4;                   // counted: dc never wraps
+    for (uint32_t c0 = (uint32_t)lane; c0 < nchunk; c0 += kCopyUnroll * kWave) {
+        u32x4 A[kCopyUnroll], B[kCopyUnroll];
+        uint32_t sa[kCopyUnroll];
+        // every load of the pass first, unconditional (a chunk past the end reads the
+        // descriptor's out-of-range offset: zeros, no traffic)
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; ++u) {
+            const uint32_t c = c0 + u * kWave;
+            // source address of destination byte dc (before the frame's start for the first
+            // chunk: those addresses wrap past the range and read as 0; their bytes are not
+            // kept)
+            sa[u] = c < nchunk ? (s0 + (dbase + 16u * c - d0)) & ~15u : fb;
+            A[u] = load16_fast<kCopyAux>(rs, sa[u]);
+            B[u] = load16_fast<kCopyAux>(rs, sh != 0u && c < nchunk ? sa[u] + 16u : fb);
+        }
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; ++u) {
+            const uint32_t c = c0 + u * kWave;
+            if (c >= nchunk) break;
+            const uint32_t dc = dbase + 16u * c;
+            u32x4 a = A[u], b = B[u];
+            // a chunk that straddles the buffer's end was dropped whole: re-read it (rare)
+            if (__builtin_expect(straddles(sa[u], fb), 0)) a = load16(rs, sa[u], fb);
+            if (__builtin_expect(sh != 0u && straddles(sa[u] + 16u, fb), 0))
+                b = load16(rs, sa[u] + 16u, fb);
+            const uint32_t W[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            uint32_t T[5];
+#pragma unroll
+            for (int m = 0; m < 5; ++m)
+                T[m] = q == 0u ? W[m] : (q == 1u ? W[m + 1] : (q == 2u ? W[m + 2] : W[m + 3]));
+            u32x4 v;
+            v.x = align_bytes(T[1], T[0], r);
+            v.y = align_bytes(T[2], T[1], r);
+            v.z = align_bytes(T[3], T[2], r);
+            v.w = align_bytes(T[4], T[3], r);
+            const int lo = dc < d0 ? (int)(d0 - dc) : 0;
+            const int hi = dend - dc < 16u ? (int)(dend - dc) : 16;
+            if (SUM) acc += chunk_sum(v, lo, hi);
+            if (lo == 0 && hi == 16) {
+                __builtin_amdgcn_raw_buffer_store_b128(v, ro, (int)dc, 0, kCopyAux);
+            } else {
+                store_dword_part(ro, dc, v.x, lo, hi);
+                store_dword_part(ro, dc + 4u, v.y, lo - 4, hi - 4);
+                store_dword_part(ro, dc + 8u, v.z, lo - 8, hi - 8);
+                store_dword_part(ro, dc + 12u, v.w, lo - 12, hi - 12);
+            }
+        }
+    }
+    return acc;
+}
+
+// the fields a segment's header differs in: n bytes at frame offset off, value in memory order
+struct SegPatch {
+    uint32_t off, n, val;
+};
+constexpr int kSegPatches = 5;
+
+// The header [s0, s0 + len) goes to [d0, d0 + len) a lane per 4-B aligned destination dword
+// (headers are a few dwords: one pass as a rule).  header_dword: the source bytes of
+// destination dword c.
+__device__ __forceinline__ uint32_t header_dword(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 uint32_t s0, uint32_t d0, uint32_t c) {
+    return gdword(rs, fb, s0 + ((d0 & ~3u) + 4u * c - d0));
+}
+
+// Copy the header with the patches applied.  `first`: header_dword of this lane's first
+// dword (c = lane), which the caller loaded along with the payload.
+__device__ __forceinline__ void wave_copy_header(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 __amdgpu_buffer_rsrc_t ro, uint32_t s0,
+                                                 uint32_t d0, uint32_t len, uint32_t first,
+                                                 const SegPatch (&P)[kSegPatches], int lane) {
+    const uint32_t dend = d0 + len;
+    const uint32_t ndw = (dend - (d0 & ~3u) + 3u) >> 2;
+    for (uint32_t c = (uint32_t)lane; c < ndw; c += kWave) {
+        const uint32_t dd = (d0 & ~3u) + 4u * c;
+        const int rel = (int)(dd - d0);                 // header offset of the dword's byte 0
+        uint32_t v = c < (uint32_t)kWave ? first : header_dword(rs, fb, s0, d0, c);
+#pragma unroll
+        for (int k = 0; k < kSegPatches; ++k) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t idx = (uint32_t)(rel + b) - P[k].off;
+                if (idx < P[k].n)
+                    v = (v & ~(0xffu << (8 * b))) | (((P[k].val >> (8u * idx)) & 0xffu) << (8 * b));
+            }
+        }
+        store_dword_part(ro, dd, v, rel < 0 ? -rel : 0, dend - dd < 4u ? (int)(dend - dd) : 4);
+    }
+}
+
+// Output j, the k-th of the input frame with plan (pa, pb) and output byte base `base`: its
+// offset entry and its bytes, the whole wave.
+__device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                             __amdgpu_buffer_rsrc_t ro,
+                                             uint32_t* __restrict__ out_offsets, uint32_t mss,
+                                             uint32_t j, uint32_t k, u32x4 pa, u32x4 pb,
+                                             uint32_t base, int lane) {
+    const uint32_t foff = pa.x, flen = pa.y;
+    if (!(pb.w & kSegOn)) {                                       // pass-through: a byte copy
+        if (lane == 0) out_offsets[j + 1] = base + flen;
+        wave_copy<false>(rs, fb, ro, foff, base, flen, lane);
+        return;
+    }
+    const bool v6 = (pb.w & kSegV6) != 0u;
+    const uint32_t l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu, pl = pa.w >> 16;
+    const uint32_t done = k * mss;                                // < pl: k < ceil(pl / mss)
+    const uint32_t left = done < pl ? pl - done : 0u;
+    const uint32_t pk = left < mss ? left : mss;
+    const bool last = left <= mss;
+    const uint32_t d0 = base + k * (po + mss);
+    if (lane == 0) out_offsets[j + 1] = d0 + po + pk;
+    // the payload slice first: its sum goes into the header, whose bytes are fetched along
+    // with it (a lane past the header reads a dword it does not keep)
+    const uint32_t hfirst = header_dword(rs, fb, foff, d0, (uint32_t)lane);
+    const uint32_t part = wave_copy<true>(rs, fb, ro, foff + po + done, d0 + po, pk, lane);
+    const uint32_t pay = be_sum(wave_sum(fold16(part)), d0 + po);
+
+    SegPatch P[kSegPatches];
+    if (!v6) {
+        const uint32_t tot = po - l3 + pk, ident = ((pb.x >> 16) + k) & 0xffffu;
+        const uint32_t ck = ~fold16((pb.x & 0xffffu) + tot + ident) & 0xffffu;
+        P[0] = SegPatch{l3 + 2u, 4u, bswap16(tot) | (bswap16(ident) << 16)};
+        P[1] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
+    } else {
+        P[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + pk) & 0xffffu)};
+        P[1] = SegPatch{0u, 0u, 0u};
+    }
+    const uint32_t seq = pb.z + done;
+    uint32_t w12 = pb.y >> 16;
+    if (!last) w12 &= ~0x09u;                                     // FIN, PSH: the last segment's
+    if (k != 0u) w12 &= ~0x80u;                                   // CWR: the first segment's
+    const uint32_t tlen = po - l4 + pk;
+    const uint32_t tck = ~fold16((pb.y & 0xffffu) + (seq >> 16) + (seq & 0xffffu) + w12 + tlen + pay) &
+                         0xffffu;
+    P[2] = SegPatch{l4 + 4u, 4u, bswap32(seq)};
+    P[3] = SegPatch{l4 + 13u, 1u, w12 & 0xffu};
+    P[4] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
+    wave_copy_header(rs, fb, ro, foff, d0, po, hfirst, P, lane);
+}
+
+// A wave writes kSegRun consecutive outputs.  What precedes an output's first copy load is a
+// chain of dependent loads (the totals, the search, the plan), microseconds against the
+// fraction of one that 1.5 KB take to copy; with one output a wave that chain bounded the
+// kernel at 0.55 of the same bytes' device copy.  Here the search is done once for the run,
+// and the outputs after the first find their frame by stepping along seg_first.
+#ifndef RPKT_SEG_RUN
+#define RPKT_SEG_RUN 8
+#endif
+constexpr uint32_t kSegRun = RPKT_SEG_RUN;
+
+__global__ __launch_bounds__(kSegBlock)
+void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n, uint32_t mss,
+                          const u32x4* __restrict__ plan, const uint32_t* __restrict__ seg_first,
+                          const uint64_t* __restrict__ obase, const uint64_t* __restrict__ totals,
+                          uint8_t* __restrict__ out, uint32_t out_bytes,
+                          uint32_t* __restrict__ out_offsets, uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t j64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kSegRun;
+    if (j64 >= out_cap) return;                                   // wave-uniform, as all below
+    const uint32_t j0 = (uint32_t)j64;
+    const uint32_t j1 = out_cap - j0 < kSegRun ? out_cap : j0 + kSegRun;   // outputs [j0, j1)
+    const uint64_t n_out = totals[0], need = totals[1];
+    if (n_out > out_cap || need > out_bytes) return;              // overflow: the totals say so
+    // spare slots are empty frames at the end
+    if ((uint32_t)lane < j1 - j0 && j0 + (uint32_t)lane >= n_out)
+        out_offsets[j0 + (uint32_t)lane + 1u] = (uint32_t)need;
+    if (j0 >= n_out) return;
+    if (j0 == 0u && lane == 0) out_offsets[0] = 0u;
+    // the input frame of output j0: the last i with seg_first[i] <= j0 (every frame has an
+    // output, so i <= j0).  64 probes a round, one per lane: three dependent loads at
+    // n = 32,768 where a binary search has fifteen.
+    uint32_t lo = 0, hi = j0 < n - 1u ? j0 : n - 1u;
+    while (lo < hi) {
+        const uint32_t step = (hi - lo) / kWave + 1u;
+        const uint64_t at = (uint64_t)lo + (uint64_t)(lane + 1) * step;
+        const bool le = at <= hi && seg_first[at] <= j0;          // true on the first c lanes
+        const uint32_t c = (uint32_t)__popcll(__ballot(le));
+        lo += c * step;
+        hi = hi - lo < step - 1u ? hi : lo + step - 1u;
+    }
+    uint32_t i = lo, cur = seg_first[i], nxt = seg_first[i + 1];
+    u32x4 pa = plan[2 * (size_t)i], pb = plan[2 * (size_t)i + 1];
+    uint32_t base = (uint32_t)obase[i];                           // < need <= out_bytes < 4 GiB
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    const uint32_t jend = j1 < n_out ? j1 : (uint32_t)n_out;
+    for (uint32_t j = j0; j < jend; ++j) {
+        if (j >= nxt) {                                           // the next frame's first output
+            while (j >= nxt && i + 1u < n) {
+                ++i;
+                cur = nxt;
+                nxt = seg_first[i + 1];
+            }
+            pa = plan[2 * (size_t)i];
+            pb = plan[2 * (size_t)i + 1];
+            base = (uint32_t)obase[i];
+        }
+        write_output(rs, fb, ro, out_offsets, mss, j, j - cur, pa, pb, base, lane);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rpkt_gpu_segment_workspace_bytes(uint32_t n) { return seg_ws_bytes(n); }
+
+int rpkt_gpu_segment_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev, uint32_t mss,
+                           uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
+                           uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
+                           uint64_t* totals_dev, void* workspace_dev, void* stream) {
+    if (!b || any_null(recs_dev, out_frames_dev, out_offsets_dev, seg_first_dev, totals_dev) ||
+        !workspace_dev)
+        return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, 0u));
+    if (mss == 0u || mss > 65535u) return RPKT_E_INVAL;
+    if (b->n == 0) return RPKT_OK;
+    RPKT_TRY(frames_ok(*b));
+    RPKT_TRY(size_ok(b->frames_bytes));
+    RPKT_TRY(size_ok(out_bytes));
+    RPKT_TRY(layout_ok(*b));
+    if (out_cap == 0u) return RPKT_E_INVAL;
+    if (misaligned(15, recs_dev, out_frames_dev) || misaligned(15, (const uint8_t*)workspace_dev) ||
+        misaligned(7, totals_dev))
+        return RPKT_E_ALIGN;
+
+    const SegWs ws = seg_ws(workspace_dev, b->n);
+    const uint32_t nb = seg_blocks(b->n);
+    hipStream_t st = (hipStream_t)stream;
+    RPKT_TRY(launch_batch(segment_plan_kernel, kSegBlock, 0, stream, *b, recs_dev, mss, ws.plan,
+                          seg_first_dev, ws.obase, ws.part));
+    RPKT_TRY(launch(segment_scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, b->n,
+                    seg_first_dev, totals_dev));
+    RPKT_TRY(launch(segment_scan_frames_kernel, dim3(nb), dim3(kSegBlock), 0, st, b->n, ws.part,
+                    seg_first_dev, ws.obase));
+    const uint64_t per_block = (uint64_t)kWavesPerBlock * kSegRun;        // outputs a block
+    const uint32_t wb = (uint32_t)(((uint64_t)out_cap + per_block - 1) / per_block);
+    return launch(segment_write_kernel, dim3(wb), dim3(kSegBlock), 0, st, b->frames_dev,
+                  (uint32_t)b->frames_bytes, b->n, mss, ws.plan, seg_first_dev, ws.obase, totals_dev,
+                  out_frames_dev, (uint32_t)out_bytes, out_offsets_dev, out_cap);
+}
+
+}  // extern "C"

@@ -80,6 +80,9 @@ ABI = {
     "rpkt_gpu_build_batch": (_i, [_B, _p, _u32, _p, _p]),
     "rpkt_gpu_build_tunnel_batch": (_i, [_B, _p, _p, _u32, _p, _p]),
     "rpkt_gpu_forward_batch": (_i, [_B, ctypes.POINTER(Fwd), _p, _p]),
+    "rpkt_gpu_segment_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_segment_batch": (_i, [_B, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
+                                    _p]),
     "rpkt_gpu_options_batch": (_i, [_B, _p, _p, _p]),
     "rpkt_gpu_options_batch_compact": (_i, [_B, _p, _p, _p]),
     "rpkt_gpu_parse_options_batch": (_i, [_B, _u32, _p, _p, _p, _u32, _p]),
@@ -577,6 +580,50 @@ def forward_batch(batch, dmac, smac, forbid=None, keep=None, stream=None, flags=
     _call("rpkt_gpu_forward_batch", ctypes.byref(batch.desc()), ctypes.byref(f), keep.data_ptr(),
           _stream_ptr(stream))
     return keep
+
+
+def segment_workspace(n, device="cuda"):
+    """The workspace tensor of segment_batch for n input frames
+    (rpkt_gpu_segment_workspace_bytes)."""
+    return _bytes(max(int(lib().rpkt_gpu_segment_workspace_bytes(n)), 16), 1, device)
+
+
+def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=None,
+                  out_bytes=None, seg_first=None, totals=None, workspace=None, stream=None,
+                  header_max=None):
+    """rpkt_gpu_segment_batch: TCP segmentation (TSO) of `batch` at `mss`, located by `recs`
+    (parse_batch's records of this batch).  Returns (out, seg_first, totals): `out` a packed
+    DeviceBatch over out_cap slots (slots past totals[0] are empty frames), seg_first an int32
+    tensor of n + 1 (the outputs of frame i are [seg_first[i], seg_first[i + 1])), totals an
+    int64 tensor {n_out, out_bytes_needed}.  Nothing here reads the device: when totals
+    exceeds out_cap / out_bytes the batch overflowed and `out` is unspecified.
+    By default the outputs are sized from the documented bound: out_cap = n +
+    frames_bytes // mss slots and out_bytes = frames_bytes + (out_cap - n) * header_max bytes,
+    header_max (the longest payload_off of the batch) 134 unless given: Ethernet, two tags and
+    60-B IPv4 and TCP headers; give it for IPv6 frames with long extension chains."""
+    torch = _torch()
+    dev = batch.frames.device
+    n, fbytes = batch.n, batch.frames.numel()
+    if out_cap is None:
+        out_cap = out_offsets.numel() - 1 if out_offsets is not None else n + fbytes // mss
+    if out_bytes is None:
+        out_bytes = out_frames.numel() if out_frames is not None else \
+            fbytes + (out_cap - n) * (134 if header_max is None else header_max)
+    if out_frames is None:
+        out_frames = _bytes(max(out_bytes, 16), 1, dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(out_cap + 1, dtype=torch.int32, device=dev)
+    if out_frames.numel() < out_bytes or out_offsets.numel() < out_cap + 1:
+        raise RpktError("segment_batch: outputs smaller than out_bytes / out_cap + 1")
+    seg_first = torch.empty(n + 1, dtype=torch.int32, device=dev) if seg_first is None else seg_first
+    totals = torch.empty(2, dtype=torch.int64, device=dev) if totals is None else totals
+    workspace = segment_workspace(n, dev) if workspace is None else workspace
+    if recs.numel() != n * REC_BYTES or seg_first.numel() < n + 1:
+        raise RpktError("segment_batch: records or seg_first do not fit %d frames" % n)
+    _call("rpkt_gpu_segment_batch", ctypes.byref(batch.desc()), recs.data_ptr(), mss, 0,
+          out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, seg_first.data_ptr(),
+          totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
 
 
 def options_batch(batch, recs, opts=None, stream=None, compact=False):

@@ -1,0 +1,168 @@
+"""Time rpkt_gpu_segment_batch against a device-to-device copy of the same bytes (GPU box):
+
+    python tools/segment_time.py [--out profiles/segment/times.json]
+
+Workload: 32,768 Ether/IPv4/TCP super-frames of 54 + 32,768 B with random payload, strided,
+mss 1448: 23 segments a frame, about 1 GiB in and 1.04 GiB out, past the 256-MB Infinity
+Cache.  Two such batches (two seeds) are rotated; the records come from a parse of each.
+
+Timed as bench.py times a leg: warm-up launches for at least 0.3 s, then two HIP events on
+the launch stream around LAUNCHES back-to-back calls (default 50), the segmentation and the
+copy in interleaved rounds (the first round thrown away; the figure is the median of the
+others).  The copy is torch's Tensor.copy_ of the input frames into the output buffer: it
+reads and writes frames_bytes each, about the bytes the segmentation moves, and is the
+yardstick as DESIGN.md section 6 uses a same-run copy for the headline.  Fractions are of 8 TB/s.
+
+The split of the time between plan + scan and write comes from a run of its own:
+
+    rocprofv3 --kernel-trace --stats -d DIR -o seg -- python tools/segment_time.py --trace-launches 6
+
+The run also checks the output: 23 segments a frame, and a parse of it with both sums finds
+every segment OK with valid IPv4 and TCP sums."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HDR, PAYLOAD, MSS = 54, 32768, 1448
+HBM_BYTES_PER_S = 8e12
+
+
+def rfc1071(b):
+    s = int(b.reshape(-1, 2).astype(np.uint32).dot(np.array([256, 1], dtype=np.uint32)).sum())
+    while s >> 16:
+        s = (s & 0xffff) + (s >> 16)
+    return (~s) & 0xffff
+
+
+def super_frames(n, seed):
+    """(n, 54 + 32768) uint8: one header (the TCP checksum left 0: segmentation never reads
+    it), random payload."""
+    hdr = np.zeros(HDR, dtype=np.uint8)
+    hdr[0:12] = (2, 0, 0, 0, 0, 1, 2, 0, 0, 0, 0, 2)
+    hdr[12:14] = (8, 0)
+    tot = 40 + PAYLOAD
+    hdr[14:24] = (0x45, 0, tot >> 8, tot & 255, 0x12, 0x34, 0x40, 0, 64, 6)
+    hdr[26:34] = (10, 0, 0, 1, 10, 0, 0, 2)
+    ck = rfc1071(hdr[14:34])
+    hdr[24:26] = (ck >> 8, ck & 255)
+    hdr[34:38] = (0x13, 0x88, 0x01, 0xbb)
+    hdr[38:42] = (0x10, 0x20, 0x30, 0x40)
+    hdr[46:48] = (0x50, 0x18)                                     # header_len 20, ACK | PSH
+    hdr[48:50] = (0x20, 0x00)
+    f = np.frombuffer(np.random.default_rng(seed).bytes(n * (HDR + PAYLOAD)),
+                      dtype=np.uint8).reshape(n, HDR + PAYLOAD).copy()
+    f[:, :HDR] = hdr
+    return f
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/segment/times.json")
+    ap.add_argument("--n", type=int, default=32768)
+    ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--trace-launches", type=int, default=0,
+                    help="no timing: this many calls, for a kernel-trace pass")
+    a = ap.parse_args()
+    import time
+
+    import torch
+    from rpkt_amd import engine
+    from rpkt_amd.records import as_records
+
+    stream = torch.cuda.current_stream()
+    n, flen = a.n, HDR + PAYLOAD
+    per = -(-PAYLOAD // MSS)
+    n_out, need = n * per, n * (per * HDR + PAYLOAD)
+    dbs, recs = [], []
+    for seed in (31, 3131):
+        db = engine.DeviceBatch(torch.from_numpy(super_frames(n, seed).reshape(-1)).to("cuda"), n,
+                                stride=flen)
+        dbs.append(db)
+        recs.append(engine.parse_batch(db, 0))
+    R = len(dbs)
+    out_frames = torch.empty(need, dtype=torch.uint8, device="cuda")
+    out_offsets = torch.empty(n_out + 1, dtype=torch.int32, device="cuda")
+    seg_first = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    totals = torch.zeros(2, dtype=torch.int64, device="cuda")
+    ws = engine.segment_workspace(n)
+
+    def segment(k):
+        engine.segment_batch(dbs[k % R], recs[k % R], MSS, out_frames=out_frames,
+                             out_offsets=out_offsets, seg_first=seg_first, totals=totals,
+                             workspace=ws, stream=stream)
+
+    def copy(k):
+        out_frames[:n * flen].copy_(dbs[k % R].frames)
+
+    if a.trace_launches:
+        for k in range(a.trace_launches):
+            segment(k)
+        torch.cuda.synchronize()
+        return
+    legs = {"segment_batch": segment, "device_copy": copy}
+    k, t_w = 0, time.perf_counter()
+    while k < 8 or time.perf_counter() - t_w < 0.3:
+        copy(k)
+        segment(k)
+        k += 1
+        if k % 8 == 0:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for r in range(a.rounds + 1):
+        for name, fn in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for j in range(a.launches):
+                fn(j)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if r:
+                ms[name].append(e0.elapsed_time(e1) / a.launches)
+    med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+
+    # the workload is what it claims (the last call ran on batch (launches - 1) % R)
+    segment(0)
+    torch.cuda.synchronize()
+    assert totals.cpu().tolist() == [n_out, need], totals.cpu().tolist()
+    first = seg_first.cpu().numpy().view(np.uint32)
+    assert np.array_equal(first, np.arange(n + 1, dtype=np.uint32) * per)
+    odb = engine.DeviceBatch(out_frames, n_out, out_offsets)
+    orec = as_records(engine.parse_batch(odb, 3).cpu().numpy())
+    assert (orec["status"] == 0).all() and (orec["ip_sum"] == 0xffff).all()
+    assert (orec["l4_sum"] == 0xffff).all()
+    last = np.arange(n_out) % per == per - 1
+    assert (orec["payload_len"][~last] == MSS).all()
+    assert (orec["payload_len"][last] == PAYLOAD - (per - 1) * MSS).all()
+
+    moved = {"frames_in": n * flen, "records_in": n * 80, "frames_out": need,
+             "offsets_out": (n_out + 1) * 4}
+    alg = sum(moved.values())
+    res = {"device": engine.device_info(), "build": engine.lib().rpkt_gpu_build_info().decode(),
+           "frames": n, "frame_len": flen, "mss": MSS, "segments": n_out, "bytes": moved,
+           "batches_rotated": R, "launches_per_round": a.launches, "rounds": a.rounds, "ms": {}}
+    for name, v in med.items():
+        res["ms"][name] = {"ms": round(v, 4), "rounds_ms": [round(x, 4) for x in ms[name]]}
+    res["ms"]["segment_batch"]["bytes"] = alg
+    res["ms"]["segment_batch"]["fraction_of_8TBs"] = round(
+        alg / (med["segment_batch"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    res["ms"]["device_copy"]["bytes"] = 2 * n * flen
+    res["ms"]["device_copy"]["fraction_of_8TBs"] = round(
+        2 * n * flen / (med["device_copy"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    res["segment_over_copy_per_byte"] = round(
+        (med["segment_batch"] / alg) / (med["device_copy"] / (2 * n * flen)), 4)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
