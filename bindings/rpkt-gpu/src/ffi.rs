@@ -71,6 +71,8 @@ pub const RPKT_F_FLOW_EV: u32 = 4;
 pub const RPKT_F_IPV6: u32 = 8;
 pub const RPKT_BUILD_IP_CSUM: u32 = 1;
 pub const RPKT_BUILD_L4_CSUM: u32 = 2;
+/// rpkt_gpu_coalesce_batch: do not require valid sums in the records
+pub const RPKT_COALESCE_TRUST_SUMS: u32 = 1;
 
 // enum rpkt_opt_stop / rpkt_layer_stop
 pub const RPKT_OPT_NONE: u8 = 0;
@@ -388,6 +390,19 @@ extern "C" {
                                   out_offsets_dev: *mut u32, out_cap: u32,
                                   seg_first_dev: *mut u32, totals_dev: *mut u64,
                                   workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_coalesce_batch for n positions.
+    pub fn rpkt_gpu_coalesce_workspace_bytes(n: u32) -> usize;
+    /// TCP receive coalescing (GRO / LRO) on the device: consecutive in-order TCP segments of
+    /// one flow, taken in `order_dev`'s order (NULL: frame order), are merged into one frame
+    /// with fixed-up lengths and fresh checksums, every other frame copied; the output is a
+    /// packed batch of `out_cap` slots.  `order_dev` and `out_mss_dev` may be NULL.
+    pub fn rpkt_gpu_coalesce_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
+                                   order_dev: *const u32, max_payload: u32, flags: u32,
+                                   out_frames_dev: *mut u8, out_bytes: u64,
+                                   out_offsets_dev: *mut u32, out_cap: u32,
+                                   src_first_dev: *mut u32, out_mss_dev: *mut u16,
+                                   totals_dev: *mut u64, workspace_dev: *mut c_void,
+                                   stream: *mut c_void) -> c_int;
     pub fn rpkt_gpu_build_tunnel_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
                                        tun_dev: *const rpkt_tun_t, flags: u32, built_dev: *mut u8,
                                        stream: *mut c_void) -> c_int;

@@ -445,6 +445,48 @@ pub unsafe fn segment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mss
                                       out.totals_dev, workspace_dev, stream))
 }
 
+/// The outputs of rpkt_gpu_coalesce_batch: a packed batch of `out_cap` slots (`frames_dev`,
+/// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first
+/// position of every output (`src_first_dev`, `n + 1` entries), each merged output's segment
+/// size (`out_mss_dev`, `n` entries, or null) and `totals_dev` (u64[2], 8-byte aligned: the
+/// output frame count and the output bytes needed).
+pub struct CoalesceOut {
+    pub frames_dev: *mut u8,
+    pub out_bytes: u64,
+    pub offsets_dev: *mut u32,
+    pub out_cap: u32,
+    pub src_first_dev: *mut u32,
+    pub out_mss_dev: *mut u16,
+    pub totals_dev: *mut u64,
+}
+
+/// rpkt_gpu_coalesce_workspace_bytes: the workspace of coalesce_batch for `n` positions.
+pub fn coalesce_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_coalesce_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_coalesce_batch: TCP receive coalescing (GRO) of a parsed batch, its positions
+/// taken in `order_dev`'s order (null: frame order), merged payloads of at most `max_payload`
+/// (1..65535) bytes.  `trust_sums`: do not require valid checksum verdicts in the records
+/// (RPKT_COALESCE_TRUST_SUMS).
+///
+/// # Safety
+/// `batch` must describe device memory valid for the call; `recs_dev` must be the records a
+/// parse wrote for this same batch; `order_dev` must be null or hold `batch.n` entries; every
+/// pointer of `out` must be device memory of the size its field documents (`out_mss_dev` may
+/// be null), and `workspace_dev` must hold `coalesce_workspace_bytes(batch.n)` bytes (16-byte
+/// aligned), all on the same device.
+pub unsafe fn coalesce_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec,
+                             order_dev: *const u32, max_payload: u32, trust_sums: bool,
+                             out: &CoalesceOut, workspace_dev: *mut core::ffi::c_void,
+                             stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    let flags = if trust_sums { ffi::RPKT_COALESCE_TRUST_SUMS } else { 0 };
+    check(ffi::rpkt_gpu_coalesce_batch(batch, recs_dev, order_dev, max_payload, flags,
+                                       out.frames_dev, out.out_bytes, out.offsets_dev, out.out_cap,
+                                       out.src_first_dev, out.out_mss_dev, out.totals_dev,
+                                       workspace_dev, stream))
+}
+
 /// rpkt_gpu_parse_tunnel_next: the next tunnel level (nested tunnels) from the tunnel and
 /// inner records of the level before, without flow events.
 ///

@@ -105,7 +105,10 @@ enum rpkt_status {
  *     totals_dev) or workspace_dev (E_INVAL); flags other than 0, then mss outside 1..65535
  *     (E_INVAL); n == 0 (RPKT_OK); NULL frames_dev (E_INVAL); frames_bytes, then out_bytes at
  *     the same limit (E_TOO_LARGE); no layout (E_INVAL); out_cap == 0 (E_INVAL); alignment
- *     (E_ALIGN): recs_dev, out_frames_dev, workspace_dev 16 B, totals_dev 8 B.
+ *     (E_ALIGN): recs_dev, out_frames_dev, workspace_dev 16 B, totals_dev 8 B;
+ *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
+ *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags other than
+ *     RPKT_COALESCE_TRUST_SUMS, then max_payload outside 1..65535 in mss's place.
  * Where an entry leaves that order (kept as it is, callers may rely on it):
  *   rpkt_gpu_parse_tunnel_batch and each slot of rpkt_gpu_parse_tunnel_ring test the flow
  *     events first, before n == 0: an empty batch with RPKT_F_FLOW_EV and no event buffer is
@@ -758,6 +761,86 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev
                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                            uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                            uint64_t* totals_dev, void* workspace_dev, void* stream);
+
+/* ---- TCP receive coalescing (GRO / LRO) ------------------------------------------- */
+
+/* The receive-side counterpart of rpkt_gpu_segment_batch: rpkt-dpdk/examples/lro_rx.rs turns
+ * on the port's LRO offload (rx_offloads bit 4, with scatter) and reads each COALESCED TCP
+ * frame's seq_num, ack_num, psh, window_size and payload_len (lro_rx.rs:81-99).
+ * rpkt_gpu_coalesce_batch merges consecutive in-order TCP segments of one flow into one frame
+ * on the device, for frames that stay in HBM, so a receive loop pays one record and one
+ * downstream step per application write instead of one per wire segment.  The output is the
+ * complete batch in position order: every position ends up in exactly one output frame.
+ *
+ * recs_dev: the rpkt_rec_t records of a parse of this same batch (RPKT_F_IPV6 for IPv6
+ * frames; RPKT_F_IP_SUM | RPKT_F_L4_SUM unless RPKT_COALESCE_TRUST_SUMS).  As for
+ * rpkt_gpu_segment_batch the records locate things and give the verdicts -- status, the
+ * dispatch ethertype, ip_protocol, ip_frag, l3_off, l4_off, payload_off, payload_len,
+ * ip6_pdst_off, ip_sum, l4_sum -- and every header byte is taken from the frame.
+ * order_dev (optional, n entries): position i holds frame order[i] (NULL: frame i), for
+ * bursts whose flows interleave (a stable sort of the flow events' buckets).  An entry >= n
+ * makes its position an empty frame: never read, a zero-length output.  It need not be a
+ * permutation.  max_payload: 1..65535, the largest merged TCP payload.  flags: 0 or
+ * RPKT_COALESCE_TRUST_SUMS.
+ *
+ * A frame is ELIGIBLE iff status == RPKT_S_OK, ip_protocol == 6, for IPv4
+ * (ip_frag & 0x3fff) == 0, payload_len >= 1, its offsets nest as segmentation requires, SYN
+ * (0x02), RST (0x04) and URG (0x20) are clear in TCP byte 13 and, without TRUST_SUMS,
+ * l4_sum == 0xffff and for IPv4 ip_sum == 0xffff (a coalescer that refreshes checksums must
+ * not launder a corrupt segment).
+ * B(i), "position i continues position i - 1" (B(0) false): both frames eligible, the same IP
+ * version, equal l3_off, l4_off and payload_off; header bytes [0, payload_off) equal, ignoring
+ * only IPv4 bytes l3+2..5 (length, ident) and l3+10..11 (checksum), IPv6 bytes l3+4..5, TCP
+ * bytes l4+4..7 (seq), the FIN, PSH and CWR bits of byte l4+13 and bytes l4+16..17 (checksum)
+ * -- so MACs, tags, addresses, TOS, TTL, DF, IP options and extension headers, ports, ack,
+ * window, the other flag bits and every TCP option byte match; seq_i == seq_{i-1} +
+ * payload_len_{i-1} (mod 2^32); for IPv4 with DF clear ident_i == ident_{i-1} + 1 (mod 2^16),
+ * with DF set ident is ignored; frame i - 1 carries neither FIN nor PSH; frame i no CWR.
+ * With p = payload_len:  short(i) = B(i) && p_i < p_{i-1};
+ *                        link(i)  = B(i) && p_i <= p_{i-1} && !short(i-1).
+ * So within a run of links every frame but the last has the head's payload length, and a
+ * short frame ends its run.  The rule looks at three neighbouring positions only (it is not
+ * Linux's sequential state machine): it loses a merge only after two successive shrinking
+ * segments.  A run is cut greedily into groups: a linked frame joins the current group while
+ * the group's payload stays <= min(max_payload, 65535 - ip_hdrs), ip_hdrs = payload_off -
+ * l3_off (IPv4) or payload_off - l3_off - 40 (IPv6).
+ *
+ * Outputs, in position order, one per group:
+ *   a group of one frame   a byte copy of [0, frame_len), padding included;
+ *   a merged group         the head's bytes [0, payload_off), then every member's
+ *                          [payload_off, + payload_len) in order (Ethernet padding is not
+ *                          carried); IPv4 packet_len / IPv6 payload_len set for the total; the
+ *                          head's IPv4 ident; the IPv4 checksum filled as RPKT_BUILD_IP_CSUM
+ *                          fills it; the head's TCP seq, ack, window and options; flags = the
+ *                          head's ORed with the last member's FIN and PSH; the TCP checksum
+ *                          filled as segmentation fills it (the IPv6 pseudo destination from the
+ *                          head's ip6_pdst_off under rpkt_gpu_build_batch's rule; 0 stays 0);
+ *   src_first_dev  n + 1 entries: output j is made of positions [src_first[j],
+ *                  src_first[j+1]); entries n_out+1..n equal n; exact whatever the capacities;
+ *   out_mss_dev    optional, n entries: the head's payload_len for a merged output, 0 for a
+ *                  copied one and for entries >= n_out -- the gso_size a later
+ *                  rpkt_gpu_segment_batch needs; exact whatever the capacities;
+ *   totals_dev, out_frames_dev, out_offsets_dev, out_cap: rpkt_gpu_segment_batch's contract
+ *                  exactly -- totals {n_out, out_bytes_needed} exact on overflow, spare offset
+ *                  slots equal out_bytes_needed, nothing written outside the buffers.
+ * Bounds for sizing: n_out <= n; out_bytes_needed <= the sum of the positions' frame lengths.
+ * workspace_dev: rpkt_gpu_coalesce_workspace_bytes(n) bytes, 16-byte aligned; calls that share
+ * one must be ordered.  The call is plan, prefix sums and write on `stream` with no host step:
+ * parse -> coalesce captures as one graph.  Records from another batch give unspecified output
+ * but never a fault: all loads go through the frames buffer resource and offsets that do not
+ * nest make a frame ineligible.
+ * Not covered: mbuf chains, the inner TCP of tunnelled frames, UDP. */
+#define RPKT_COALESCE_TRUST_SUMS 1u   /* do not require valid sums in the records */
+
+size_t rpkt_gpu_coalesce_workspace_bytes(uint32_t n);
+int rpkt_gpu_coalesce_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev,
+                            const uint32_t* order_dev,      /* optional, n entries */
+                            uint32_t max_payload, uint32_t flags,
+                            uint8_t* out_frames_dev, uint64_t out_bytes,
+                            uint32_t* out_offsets_dev, uint32_t out_cap,
+                            uint32_t* src_first_dev,        /* n + 1 entries */
+                            uint16_t* out_mss_dev,          /* optional, n entries */
+                            uint64_t* totals_dev, void* workspace_dev, void* stream);
 
 /* ---- Option iterators ----------------------------------------------------------- */
 

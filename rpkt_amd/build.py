@@ -25,11 +25,11 @@ GEN_LIB = os.path.join(OUT, "librpkt_gen.so")
 # the engine: one translation unit per kernel family, shared device code in rpkt_common.h
 GPU_SRC = [os.path.join(HERE, "csrc", f) for f in
            ("rpkt_parse.hip", "rpkt_tx.hip", "rpkt_walks.hip", "rpkt_fields.hip", "rpkt_tunnel.hip",
-            "rpkt_tunnel_chains.hip", "rpkt_tunnel_next.hip", "rpkt_segment.hip", "rpkt_abi.hip",
-            "rpkt_coll.hip")]
+            "rpkt_tunnel_chains.hip", "rpkt_tunnel_next.hip", "rpkt_segment.hip", "rpkt_coalesce.hip",
+            "rpkt_abi.hip", "rpkt_coll.hip")]
 GPU_DEPS = [os.path.join(HERE, "csrc", h) for h in
             ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h", "rpkt_chain.h", "rpkt_tunnel.h",
-             "rpkt_proto_table.h")]                                   # included; the table is generated
+             "rpkt_segcopy.h", "rpkt_proto_table.h")]                 # included; the table is generated
 # units compiled a second time with other defines (same source: same unit hash)
 SECOND_COMPILES = [("rpkt_tx.hip", "rpkt_tx_w64.o", ["-DRPKT_WIN=64", "-DRPKT_TX_W64"]),
                    # only the compact parse of short strided frames: the unit's other
@@ -49,7 +49,8 @@ UNIT_HEADERS = {"rpkt_parse.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h"
                 "rpkt_tunnel_chains.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_chain.h",
                                            "rpkt_tunnel.h"),
                 "rpkt_tunnel_next.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_tunnel.h"),
-                "rpkt_segment.hip": ("rpkt_common.h", "rpkt_args.h"),
+                "rpkt_segment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
+                "rpkt_coalesce.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
                 "rpkt_abi.hip": ("rpkt_common.h",),
                 "rpkt_coll.hip": ("rpkt_common.h",)}
 # every unit has its header list (a unit added to GPU_SRC without one would make
@@ -89,7 +90,7 @@ def unit_hashes(defines=()):
     kernel family stays valid while another unit changes: "parse=... tx=... walks=..."."""
     return " ".join("%s=%s" % (u, source_hash(["rpkt_%s.hip" % u], defines))
                     for u in ("parse", "tx", "walks", "fields", "tunnel", "tunnel_chains", "tunnel_next",
-                              "segment"))
+                              "segment", "coalesce"))
 
 
 def build_gpu(force=False, extra=()):
@@ -132,11 +133,12 @@ def build_gen(force=False):
     return GEN_LIB
 
 
-EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx")
+EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "lro_rx")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "parse_batch")
 FLOW_REDUCE_BIN = os.path.join(ROOT, "examples", "flow_reduce")
 VTEP_RX_BIN = os.path.join(ROOT, "examples", "vtep_rx")
 TSO_TX_BIN = os.path.join(ROOT, "examples", "tso_tx")
+LRO_RX_BIN = os.path.join(ROOT, "examples", "lro_rx")
 
 
 def build_example(force=False):

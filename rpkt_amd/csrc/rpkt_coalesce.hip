@@ -1,0 +1,559 @@
+// rpkt_coalesce.hip — rpkt_gpu_coalesce_batch: TCP receive coalescing (GRO / LRO) of a
+// device-resident batch, what the port's LRO offload does for rpkt-dpdk/examples/lro_rx.rs
+// and the inverse of rpkt_gpu_segment_batch (include/rpkt_gpu.h has the semantics).
+//
+// Many input positions make one output, so the work is planned per position and the bytes
+// are placed by prefix sums.  Eight launches on the stream, no host step between them:
+//   1. plan    one lane per position: its frame (through order_dev), its record (coalesced
+//              through an LDS stage, or gathered under an order) and the three header dwords
+//              eligibility and the predicate need (ident / DF, seq, the flags);
+//   2. link    one lane per position: B(i), the masked compare of its header with its
+//              predecessor's, a dword of each per step through the buffer resource; B(i - 1)
+//              from the neighbouring lane (the block's first lane computes it); link and
+//              short; the block's max-scan of run heads;
+//   3. heads   one block: the max-scan of the blocks' last run heads, with a carry;
+//   4. group   one lane per position: its run head, so its place in the run, K and whether
+//              it opens a group, is merged, or is a member; its byte contribution;
+//   5. sums    one block: exclusive prefix sums of the blocks' (outputs, bytes); the totals;
+//   6. place   one lane per position: its output index and destination; src_first, out_mss
+//              and the offsets;
+//   7. copy    one wavefront per run of kCoRun consecutive POSITIONS: a lone frame is copied
+//              whole, a member's (and a merged head's) payload goes to its destination with
+//              the funnel-shift copy of rpkt_segcopy.h, which sums what it copies at the
+//              absolute destination phase; the sum goes to the workspace;
+//   8. header  one wavefront per run of kCoHdrRun OUTPUTS: for a merged one it adds its
+//              members' sums (a lane each), sums the head's headers and writes them with the
+//              patched lengths, flags and checksums.
+// The split by input position keeps every wave's work a few frames whatever the group
+// sizes (one output of 65,495 one-byte members is 8,187 copy waves, not one wave's loop);
+// its price is the second pass over the merged outputs' headers.  No kernel waits on
+// another workgroup and every loop is bounded by a count from the plan.
+// Every load of frame bytes goes through the frames buffer resource and every store of
+// output bytes through one over [out_frames_dev, + out_bytes); an overflowing call (totals
+// past the capacities) writes its totals, src_first and out_mss and nothing else.
+#include "rpkt_common.h"
+#include "rpkt_args.h"
+#include "rpkt_segcopy.h"
+
+namespace {
+
+// the workspace: per-position plans (32 B), destinations (u64), a u32 per position (link
+// bits and the block-local run head, later the payload sum), the block sums (outputs,
+// bytes: u64 pairs) and the blocks' run heads
+struct CoWs {
+    u32x4*    plan;
+    uint64_t* obase;
+    uint32_t* aux;
+    uint64_t* part;
+    uint32_t* pmax;
+};
+inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+inline uint32_t co_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSegBlock - 1) / kSegBlock); }
+inline size_t co_ws_bytes(uint32_t n) {
+    const size_t nb = co_blocks(n);
+    return (size_t)n * 32u + up16((size_t)n * 8u) + up16((size_t)n * 4u) + nb * 16u + up16(nb * 4u);
+}
+inline CoWs co_ws(void* ws, uint32_t n) {
+    uint8_t* p = static_cast<uint8_t*>(ws);
+    CoWs w;
+    w.plan = reinterpret_cast<u32x4*>(p);
+    p += (size_t)n * 32u;
+    w.obase = reinterpret_cast<uint64_t*>(p);
+    p += up16((size_t)n * 8u);
+    w.aux = reinterpret_cast<uint32_t*>(p);
+    p += up16((size_t)n * 4u);
+    w.part = reinterpret_cast<uint64_t*>(p);
+    p += (size_t)co_blocks(n) * 16u;
+    w.pmax = reinterpret_cast<uint32_t*>(p);
+    return w;
+}
+
+// plan words: 0 frame offset, 1 frame length, 2 l3 | l4 << 16, 3 payload_off | payload_len
+// << 16 (2 and 3: 0 unless eligible), 4 seq, 5 ident | TCP byte 13 << 16, 6 kCoElig | kCoV6 |
+// kCoDF | ip6_pdst_off << 16, 7 (from group on) kCoHead | kCoMerged | the run head's
+// payload_len << 16
+constexpr uint32_t kCoElig = 1u, kCoV6 = 2u, kCoDF = 4u;
+constexpr uint32_t kCoHead = 1u, kCoMerged = 2u;
+// aux (link .. group): the block-local index + 1 of the position's run head (0: in an earlier
+// block) | kCoLink | kCoShort
+constexpr uint32_t kCoLink = 1u << 16, kCoShort = 1u << 17;
+
+constexpr uint32_t kFin = 0x01u, kSyn = 0x02u, kRst = 0x04u, kPsh = 0x08u, kUrg = 0x20u, kCwr = 0x80u;
+
+// ---- 1. plan ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
+                          const uint32_t* __restrict__ offsets, uint32_t stride, uint32_t frame_len,
+                          uint32_t n, const rpkt_rec_t* __restrict__ recs,
+                          const uint32_t* __restrict__ order, uint32_t trust,
+                          u32x4* __restrict__ plan) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    if (p0 >= n) return;                                          // wave-uniform
+
+    uint32_t f = valid ? i : n;                                   // the position's frame
+    uint32_t w0 = 0, w5 = 0, w7 = 0, w8 = 0, w16 = 0, w17 = 0, w18 = 0;
+    if (!order) {
+        uint32_t* st = stage[wave];
+        stage_records_tile(st, recs, p0, n, lane);
+        const uint32_t* w = st + lane * 21;
+        w0 = w[0], w5 = w[5], w7 = w[7], w8 = w[8], w16 = w[16], w17 = w[17], w18 = w[18];
+    } else {
+        if (valid) f = order[i];
+        if (f < n) {                                              // an entry >= n: an empty frame
+            const u32x4* r = reinterpret_cast<const u32x4*>(recs + f);
+            const u32x4 q0 = r[0], q1 = r[1], q2 = r[2], q4 = r[4];
+            w0 = q0.x, w5 = q1.y, w7 = q1.w, w8 = q2.x, w16 = q4.x, w17 = q4.y, w18 = q4.z;
+        }
+    }
+    const bool present = f < n;
+    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
+    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
+    const bool v6 = det == 0x86ddu;
+    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
+    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
+    const Frame fr = present ? frame_span(offsets, stride, frame_len, fb, f) : Frame{0u, 0u};
+    // offsets that nest as segmentation requires them to; [po, + pl) inside the frame
+    const bool nest = l4 >= l3 && po >= l4 && po <= fr.len && po - l4 >= 20u && po - l4 <= 60u &&
+                      (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
+    uint32_t pl = w17 >> 16;
+    if (nest && pl > fr.len - po) pl = fr.len - po;
+    const bool sums = trust || ((w18 >> 16) == 0xffffu && (v6 || (w18 & 0xffffu) == 0xffffu));
+    bool elig = present && status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
+                (v6 || (frag & 0x3fffu) == 0u) && nest && pl >= 1u && sums;
+    uint32_t seq = 0, idfl = 0, df = 0;
+    if (elig) {
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+        const uint32_t a3 = fr.off + l3, a4 = fr.off + l4;
+        const uint32_t t1 = gdword(rs, fb, a4 + 4u), t3 = gdword(rs, fb, a4 + 12u);
+        const uint32_t tf = (t3 >> 8) & 0xffu;                    // TCP byte 13
+        seq = bswap32(t1);
+        idfl = tf << 16;
+        if (!v6) {
+            const uint32_t ip1 = gdword(rs, fb, a3 + 4u);
+            idfl |= be16_lo(ip1);
+            df = (be16_hi(ip1) & 0x4000u) ? kCoDF : 0u;
+        }
+        elig = (tf & (kSyn | kRst | kUrg)) == 0u;
+    }
+    if (valid) {
+        plan[2 * (size_t)i] = u32x4{fr.off, fr.len, elig ? l3 | (l4 << 16) : 0u,
+                                    elig ? po | (pl << 16) : 0u};
+        plan[2 * (size_t)i + 1] = u32x4{seq, idfl, elig ? kCoElig | (v6 ? kCoV6 : 0u) | df | (pdst << 16) : 0u,
+                                        0u};
+    }
+}
+
+// ---- 2. link ---------------------------------------------------------------------------
+
+// which bits of the header dword at frame offset x enter the compare
+__device__ __forceinline__ uint32_t header_keep(uint32_t x, uint32_t l3, uint32_t l4, uint32_t po,
+                                                bool v6) {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; ++b) {
+        const uint32_t y = x + b, d3 = y - l3, d4 = y - l4;
+        uint32_t keep = 0xffu;
+        if (y >= po) keep = 0u;
+        else if (!v6 && ((d3 >= 2u && d3 <= 5u) || d3 == 10u || d3 == 11u)) keep = 0u;
+        else if (v6 && (d3 == 4u || d3 == 5u)) keep = 0u;
+        else if ((d4 >= 4u && d4 <= 7u) || d4 == 16u || d4 == 17u) keep = 0u;
+        else if (d4 == 13u) keep = 0xffu & ~(kFin | kPsh | kCwr);
+        m |= keep << (8u * b);
+    }
+    return m;
+}
+
+// the frame-relative dwords of a header in turn: one aligned load a step
+struct HeaderWalk {
+    uint32_t a4, sh, lo;
+    __device__ __forceinline__ HeaderWalk(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t s)
+        : a4(s & ~3u), sh(s & 3u), lo(ldw(rs, fb, s & ~3u)) {}
+    __device__ __forceinline__ uint32_t next(__amdgpu_buffer_rsrc_t rs, uint32_t fb) {
+        const uint32_t hi = ldw(rs, fb, a4 + 4u);
+        const uint32_t v = align_bytes(hi, lo, sh);
+        lo = hi;
+        a4 += 4u;
+        return v;
+    }
+};
+
+// B(i), i >= 1: the frame at position i continues the one at i - 1
+__device__ __forceinline__ bool base_pred(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                          const u32x4* __restrict__ plan, uint32_t i) {
+    const u32x4 pa = plan[2 * (size_t)i], pb = plan[2 * (size_t)i + 1];
+    const u32x4 qa = plan[2 * (size_t)i - 2], qb = plan[2 * (size_t)i - 1];
+    if (!(pb.z & qb.z & kCoElig) || ((pb.z ^ qb.z) & kCoV6)) return false;
+    if (pa.z != qa.z || ((pa.w ^ qa.w) & 0xffffu)) return false;          // l3, l4, payload_off
+    const bool v6 = (pb.z & kCoV6) != 0u;
+    if (pb.x != qb.x + (qa.w >> 16)) return false;                        // seq
+    if (!v6 && !(pb.z & kCoDF) && ((pb.y ^ (qb.y + 1u)) & 0xffffu)) return false;   // ident
+    if (((qb.y >> 16) & (kFin | kPsh)) || ((pb.y >> 16) & kCwr)) return false;
+    const uint32_t l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu;
+    HeaderWalk a(rs, fb, pa.x), b(rs, fb, qa.x);
+    for (uint32_t x = 0; x < po; x += 4u)                                 // po <= 65535
+        if ((a.next(rs, fb) ^ b.next(rs, fb)) & header_keep(x, l3, l4, po, v6)) return false;
+    return true;
+}
+
+// inclusive max-scan over the block's kSegBlock threads; red: kWavesPerBlock u32 of LDS
+__device__ __forceinline__ uint32_t block_incl_max(uint32_t v, uint32_t* red) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    uint32_t x = wave_incl_max(v);
+    if (lane == kWave - 1) red[wave] = x;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w)
+        if (w < wave) x = max(x, red[w]);
+    __syncthreads();                                              // red is free for the next call
+    return x;
+}
+
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_link_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
+                          const u32x4* __restrict__ plan, uint32_t* __restrict__ aux,
+                          uint32_t* __restrict__ pmax) {
+    __shared__ uint32_t bs[kSegBlock];
+    __shared__ uint32_t red[kWavesPerBlock];
+    const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
+    const bool valid = i < n;
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    const bool bi = valid && i >= 1u && base_pred(rs, fb, plan, i);
+    bs[threadIdx.x] = bi ? 1u : 0u;
+    __syncthreads();
+    bool bp;                                                      // B(i - 1)
+    if (threadIdx.x != 0u) bp = bs[threadIdx.x - 1u] != 0u;
+    else bp = valid && i >= 2u && base_pred(rs, fb, plan, i - 1u);
+    const uint32_t p = valid ? plan[2 * (size_t)i].w >> 16 : 0u;
+    const uint32_t p1 = (valid && i >= 1u) ? plan[2 * (size_t)i - 2].w >> 16 : 0u;
+    const uint32_t p2 = (valid && i >= 2u) ? plan[2 * (size_t)i - 4].w >> 16 : 0u;
+    const bool short_prev = bp && p1 < p2;
+    const bool sh = bi && p < p1;
+    const bool link = bi && p <= p1 && !short_prev;
+    const uint32_t hl = block_incl_max(valid && !link ? threadIdx.x + 1u : 0u, red);
+    if (valid) aux[i] = hl | (link ? kCoLink : 0u) | (sh ? kCoShort : 0u);
+    if (threadIdx.x == kSegBlock - 1)
+        pmax[blockIdx.x] = hl ? blockIdx.x * kSegBlock + hl : 0u; // global index + 1
+}
+
+// ---- 3. heads --------------------------------------------------------------------------
+
+// one block: pmax[b] becomes the index + 1 of the last run head in blocks 0..b
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_scan_heads_kernel(uint32_t* __restrict__ pmax, uint32_t nb) {
+    __shared__ uint32_t red[kWavesPerBlock];
+    __shared__ uint32_t last;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nb; base += kSegBlock) {
+        const uint32_t k = base + threadIdx.x;
+        const uint32_t x = max(block_incl_max(k < nb ? pmax[k] : 0u, red), carry);
+        if (k < nb) pmax[k] = x;
+        if (threadIdx.x == kSegBlock - 1) last = x;
+        __syncthreads();
+        carry = last;
+        __syncthreads();
+    }
+}
+
+// ---- 4. group --------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_group_kernel(uint32_t n, uint32_t max_payload, u32x4* __restrict__ plan,
+                           const uint32_t* __restrict__ aux, const uint32_t* __restrict__ pmax,
+                           uint64_t* __restrict__ obase, uint64_t* __restrict__ part) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
+    uint64_t cnt = 0, bytes = 0;
+    if (i < n) {
+        const uint32_t a = aux[i], hl = a & 0xffffu;
+        const bool link = (a & kCoLink) != 0u;
+        const uint32_t hp = hl ? blockIdx.x * kSegBlock + hl : (blockIdx.x ? pmax[blockIdx.x - 1u] : 0u);
+        const uint32_t h = hp ? hp - 1u : 0u;                     // the run's head, <= i
+        const u32x4 pa = plan[2 * (size_t)i];
+        const uint32_t z = plan[2 * (size_t)i + 1].z;
+        const uint32_t l3 = pa.z & 0xffffu, po = pa.w & 0xffffu, p = pa.w >> 16;
+        const uint32_t ph = plan[2 * (size_t)h].w >> 16;
+        // a linked frame has its head's offsets and IP version
+        const uint32_t iph = po - l3 - ((z & kCoV6) ? 40u : 0u);
+        const uint32_t room = 65535u - (iph < 65535u ? iph : 65535u);
+        const uint32_t limit = max_payload < room ? max_payload : room;
+        uint32_t K = ph ? limit / ph : 0u;
+        if (K == 0u) K = 1u;
+        const uint32_t r = i - h;
+        const bool ghead = !link || (r % K == 0u && K * ph + p > limit);
+        bool nhead = true;                                        // does i + 1 open a group
+        if (i + 1u < n && (aux[i + 1u] & kCoLink)) {
+            const uint32_t pn = plan[2 * (size_t)i + 2].w >> 16;
+            nhead = (r + 1u) % K == 0u && K * ph + pn > limit;
+        }
+        const bool merged = ghead && !nhead;
+        cnt = ghead ? 1u : 0u;
+        bytes = !ghead ? p : (merged ? po + p : pa.y);
+        plan[2 * (size_t)i + 1].w = (ghead ? kCoHead : 0u) | (merged ? kCoMerged : 0u) | (ph << 16);
+        obase[i] = bytes;
+    }
+    uint64_t tc, tb;
+    block_excl_scan2(cnt, bytes, tc, tb, red);
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)blockIdx.x] = tc;
+        part[2 * (size_t)blockIdx.x + 1] = tb;
+    }
+}
+
+// ---- 5. sums ---------------------------------------------------------------------------
+
+// one block: the block sums -> their exclusive prefixes, kSegBlock at a time with a carry;
+// the totals
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_scan_parts_kernel(uint64_t* __restrict__ part, uint32_t nb,
+                                uint64_t* __restrict__ totals) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    uint64_t ca = 0, cb = 0;
+    for (uint32_t base = 0; base < nb; base += kSegBlock) {
+        const uint32_t k = base + threadIdx.x;
+        uint64_t a = k < nb ? part[2 * (size_t)k] : 0, b = k < nb ? part[2 * (size_t)k + 1] : 0;
+        uint64_t ta, tb;
+        block_excl_scan2(a, b, ta, tb, red);
+        if (k < nb) {
+            part[2 * (size_t)k] = ca + a;
+            part[2 * (size_t)k + 1] = cb + b;
+        }
+        ca += ta;
+        cb += tb;
+    }
+    if (threadIdx.x == 0) {
+        totals[0] = ca;
+        totals[1] = cb;
+    }
+}
+
+// ---- 6. place --------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_place_kernel(uint32_t n, const u32x4* __restrict__ plan,
+                           const uint64_t* __restrict__ part, const uint64_t* __restrict__ totals,
+                           uint64_t* __restrict__ obase, uint32_t* __restrict__ src_first,
+                           uint16_t* __restrict__ out_mss, uint32_t* __restrict__ out_offsets,
+                           uint32_t out_cap, uint32_t out_bytes) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
+    const bool valid = i < n;
+    const uint32_t role = valid ? plan[2 * (size_t)i + 1].w : 0u;
+    uint64_t a = role & kCoHead, b = valid ? obase[i] : 0;
+    uint64_t ta, tb;
+    block_excl_scan2(a, b, ta, tb, red);
+    const uint64_t n_out = totals[0], need = totals[1];
+    const bool fits = n_out <= out_cap && need <= out_bytes;
+    if (valid) {
+        const uint64_t j = part[2 * (size_t)blockIdx.x] + a;      // < n_out <= n
+        const uint64_t dest = part[2 * (size_t)blockIdx.x + 1] + b;
+        obase[i] = dest;
+        if (role & kCoHead) {
+            src_first[j] = i;
+            if (out_mss) out_mss[j] = (role & kCoMerged) ? (uint16_t)(role >> 16) : (uint16_t)0;
+            if (fits) out_offsets[j] = (uint32_t)dest;            // j < n_out <= out_cap
+        }
+        if (i >= n_out) {
+            src_first[i] = n;
+            if (out_mss) out_mss[i] = 0;
+        }
+        if (i == 0u) src_first[n] = n;
+    }
+    // the end of the last output and the spare slots: empty frames at the end
+    if (fits) {
+        const uint64_t step = (uint64_t)gridDim.x * kSegBlock;
+        for (uint64_t k = n_out + i; k <= out_cap; k += step) out_offsets[k] = (uint32_t)need;
+    }
+}
+
+// ---- 7. copy ---------------------------------------------------------------------------
+
+// A wave copies kCoRun consecutive positions (rpkt_segment.hip's kSegRun: what precedes a
+// position's first copy load is a chain of dependent loads, here the plans and destinations
+// of the whole run fetched at once, a lane each).
+#ifndef RPKT_CO_RUN
+#define RPKT_CO_RUN 8
+#endif
+constexpr uint32_t kCoRun = RPKT_CO_RUN;
+static_assert(kCoRun <= (uint32_t)kWave, "a lane per position of the run");
+
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_copy_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
+                          const u32x4* __restrict__ plan, const uint64_t* __restrict__ obase,
+                          const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
+                          uint32_t out_bytes, uint32_t out_cap, uint32_t* __restrict__ aux) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t i64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kCoRun;
+    if (i64 >= n) return;                                         // wave-uniform, as all below
+    if (totals[0] > out_cap || totals[1] > out_bytes) return;     // overflow: the totals say so
+    const uint32_t i0 = (uint32_t)i64;
+    const uint32_t cnt = n - i0 < kCoRun ? n - i0 : kCoRun;
+    u32x4 la = {0u, 0u, 0u, 0u};
+    uint32_t lrole = 0, ldst = 0;
+    if ((uint32_t)lane < cnt) {
+        la = plan[2 * (size_t)(i0 + lane)];
+        lrole = plan[2 * (size_t)(i0 + lane) + 1].w;
+        ldst = (uint32_t)obase[i0 + lane];                        // < need <= out_bytes < 4 GiB
+    }
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t foff = (uint32_t)__shfl((int)la.x, (int)k, kWave);
+        const uint32_t flen = (uint32_t)__shfl((int)la.y, (int)k, kWave);
+        const uint32_t pw = (uint32_t)__shfl((int)la.w, (int)k, kWave);
+        const uint32_t role = (uint32_t)__shfl((int)lrole, (int)k, kWave);
+        const uint32_t dst = (uint32_t)__shfl((int)ldst, (int)k, kWave);
+        if ((role & (kCoHead | kCoMerged)) == kCoHead) {          // a lone frame: a byte copy
+            wave_copy<false>(rs, fb, ro, foff, dst, flen, lane);
+            continue;
+        }
+        // a merged head's payload follows its header; a member's is at its destination
+        const uint32_t po = pw & 0xffffu, p = pw >> 16;
+        const uint32_t d = dst + ((role & kCoHead) ? po : 0u);
+        const uint32_t part = wave_copy<true>(rs, fb, ro, foff + po, d, p, lane);
+        const uint32_t s = fold16(wave_sum(fold16(part)));
+        if (lane == 0) aux[i0 + k] = s;
+    }
+}
+
+// ---- 8. header -------------------------------------------------------------------------
+
+#ifndef RPKT_CO_HDR_RUN
+#define RPKT_CO_HDR_RUN 4
+#endif
+constexpr uint32_t kCoHdrRun = RPKT_CO_HDR_RUN;
+
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
+                            const u32x4* __restrict__ plan, const uint64_t* __restrict__ obase,
+                            const uint32_t* __restrict__ aux, const uint32_t* __restrict__ src_first,
+                            const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
+                            uint32_t out_bytes, uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t j64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kCoHdrRun;
+    const uint64_t n_out = totals[0], need = totals[1];
+    if (j64 >= n_out || n_out > out_cap || need > out_bytes) return;      // wave-uniform
+    const uint32_t j0 = (uint32_t)j64;
+    const uint32_t j1 = n_out - j0 < kCoHdrRun ? (uint32_t)n_out : j0 + kCoHdrRun;
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t j = j0; j < j1; ++j) {
+        const uint32_t i0 = src_first[j], i1 = src_first[j + 1u];        // j + 1 <= n_out <= n
+        if (i1 > n || i1 - i0 < 2u || i1 < i0) continue;                  // one frame: copied
+        const u32x4 pa = plan[2 * (size_t)i0], pb = plan[2 * (size_t)i0 + 1];
+        const uint32_t lastf = plan[2 * (size_t)i1 - 1].y >> 16;          // the last member's flags
+        const uint32_t d0 = (uint32_t)obase[i0];
+        const uint32_t end = i1 < n ? (uint32_t)obase[i1] : (uint32_t)need;
+        const uint32_t foff = pa.x, l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu;
+        const bool v6 = (pb.z & kCoV6) != 0u;
+        const uint32_t pdst = pb.z >> 16;
+        const uint32_t P = end - d0 - po;                                 // the merged payload
+        // the members' payload sums, all at the absolute destination phase
+        uint32_t s = 0;
+        for (uint32_t m = i0 + (uint32_t)lane; m < i1; m += kWave) s += aux[m];   // <= 1024 each
+        const uint32_t pay = be_sum(wave_sum(fold16(s)), d0 + po);
+        // the head's header sums, a lane each: IPv4 header, TCP header, pseudo addresses.  A
+        // field leaves a sum by adding its complement.
+        const uint32_t a3 = foff + l3, a4 = foff + l4;
+        uint32_t x = 0, y = 0;
+        if (lane == 0 && !v6) {
+            const uint32_t ip0 = gdword(rs, fb, a3), ip2 = gdword(rs, fb, a3 + 8u);
+            x = range_be_sum(rs, fb, a3, a4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ be16_hi(ip2));
+        } else if (lane == 1) {
+            const uint32_t t3 = gdword(rs, fb, a4 + 12u), t4 = gdword(rs, fb, a4 + 16u);
+            y = be16_lo(t3);
+            x = range_be_sum(rs, fb, a4, foff + po) + (0xffffu ^ y) + (0xffffu ^ be16_lo(t4));
+        } else if (lane == 2) {
+            if (!v6) {
+                x = range_be_sum(rs, fb, a3 + 12u, a3 + 20u);
+            } else {
+                // the pseudo destination: rpkt_gpu_build_batch's rule
+                const uint32_t pd = (pdst >= l3 + 24u && pdst + 16u <= l4) ? pdst : l3 + 24u;
+                x = range_be_sum(rs, fb, a3 + 8u, a3 + 24u) +
+                    range_be_sum(rs, fb, foff + pd, foff + pd + 16u);
+            }
+        }
+        const uint32_t ipc = (uint32_t)__builtin_amdgcn_readlane((int)x, 0);
+        const uint32_t tcpc = (uint32_t)__builtin_amdgcn_readlane((int)x, 1);
+        const uint32_t pseudo = (uint32_t)__builtin_amdgcn_readlane((int)x, 2);
+        uint32_t w12 = (uint32_t)__builtin_amdgcn_readlane((int)y, 1);
+        w12 |= lastf & (kFin | kPsh);
+
+        SegPatch Pt[kSegPatches];
+        if (!v6) {
+            const uint32_t tot = po - l3 + P;
+            const uint32_t ck = ~fold16(fold16(ipc) + tot) & 0xffffu;
+            Pt[0] = SegPatch{l3 + 2u, 2u, bswap16(tot & 0xffffu)};
+            Pt[1] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
+        } else {
+            Pt[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + P) & 0xffffu)};
+            Pt[1] = SegPatch{0u, 0u, 0u};
+        }
+        const uint32_t tlen = po - l4 + P;
+        const uint32_t tck = ~fold16(fold16(tcpc) + fold16(pseudo) + 6u + w12 + tlen + pay) & 0xffffu;
+        Pt[2] = SegPatch{l4 + 13u, 1u, w12 & 0xffu};
+        Pt[3] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
+        Pt[4] = SegPatch{0u, 0u, 0u};
+        const uint32_t hfirst = header_dword(rs, fb, foff, d0, (uint32_t)lane);
+        wave_copy_header(rs, fb, ro, foff, d0, po, hfirst, Pt, lane);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rpkt_gpu_coalesce_workspace_bytes(uint32_t n) { return co_ws_bytes(n); }
+
+int rpkt_gpu_coalesce_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
+                            const uint32_t* order_dev, uint32_t max_payload, uint32_t flags,
+                            uint8_t* out_frames_dev, uint64_t out_bytes, uint32_t* out_offsets_dev,
+                            uint32_t out_cap, uint32_t* src_first_dev, uint16_t* out_mss_dev,
+                            uint64_t* totals_dev, void* workspace_dev, void* stream) {
+    if (!b || any_null(recs_dev, out_frames_dev, out_offsets_dev, src_first_dev, totals_dev) ||
+        !workspace_dev)
+        return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, RPKT_COALESCE_TRUST_SUMS));
+    if (max_payload == 0u || max_payload > 65535u) return RPKT_E_INVAL;
+    if (b->n == 0) return RPKT_OK;
+    RPKT_TRY(frames_ok(*b));
+    RPKT_TRY(size_ok(b->frames_bytes));
+    RPKT_TRY(size_ok(out_bytes));
+    RPKT_TRY(layout_ok(*b));
+    if (out_cap == 0u) return RPKT_E_INVAL;
+    if (misaligned(15, recs_dev, out_frames_dev) || misaligned(15, (const uint8_t*)workspace_dev) ||
+        misaligned(7, totals_dev))
+        return RPKT_E_ALIGN;
+
+    const uint32_t n = b->n, nb = co_blocks(n), fb = (uint32_t)b->frames_bytes;
+    const CoWs ws = co_ws(workspace_dev, n);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 blk(kSegBlock), per(nb);
+    RPKT_TRY(launch_batch(coalesce_plan_kernel, kSegBlock, 0, stream, *b, recs_dev, order_dev,
+                          flags & RPKT_COALESCE_TRUST_SUMS, ws.plan));
+    RPKT_TRY(launch(coalesce_link_kernel, per, blk, 0, st, b->frames_dev, fb, n, ws.plan, ws.aux,
+                    ws.pmax));
+    RPKT_TRY(launch(coalesce_scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
+    RPKT_TRY(launch(coalesce_group_kernel, per, blk, 0, st, n, max_payload, ws.plan, ws.aux, ws.pmax,
+                    ws.obase, ws.part));
+    RPKT_TRY(launch(coalesce_scan_parts_kernel, dim3(1), blk, 0, st, ws.part, nb, totals_dev));
+    RPKT_TRY(launch(coalesce_place_kernel, per, blk, 0, st, n, ws.plan, ws.part, totals_dev, ws.obase,
+                    src_first_dev, out_mss_dev, out_offsets_dev, out_cap, (uint32_t)out_bytes));
+    const uint64_t cper = (uint64_t)kWavesPerBlock * kCoRun;             // positions a block
+    RPKT_TRY(launch(coalesce_copy_kernel, dim3((uint32_t)(((uint64_t)n + cper - 1) / cper)), blk, 0,
+                    st, b->frames_dev, fb, n, ws.plan, ws.obase, totals_dev, out_frames_dev,
+                    (uint32_t)out_bytes, out_cap, ws.aux));
+    const uint64_t hper = (uint64_t)kWavesPerBlock * kCoHdrRun;          // outputs a block
+    const uint32_t outs = n < out_cap ? n : out_cap;                     // n_out <= both, or overflow
+    return launch(coalesce_header_kernel, dim3((uint32_t)(((uint64_t)outs + hper - 1) / hper)), blk,
+                  0, st, b->frames_dev, fb, n, ws.plan, ws.obase, ws.aux, src_first_dev, totals_dev,
+                  out_frames_dev, (uint32_t)out_bytes, out_cap);
+}
+
+}  // extern "C"

@@ -1,0 +1,220 @@
+// rpkt_segcopy.h — device code the two units that re-frame a batch share (rpkt_segment.hip:
+// one frame into many; rpkt_coalesce.hip: many into one): a tile's records staged through
+// LDS, header sums by one lane, the block scan of the plan -> scan -> write structure, and
+// the wave copy between any two byte phases that sums what it copies.  Included after
+// rpkt_common.h; everything is inline in an anonymous namespace.
+#pragma once
+#include "rpkt_common.h"
+
+namespace {
+
+constexpr int kSegBlock = kWave * kWavesPerBlock;   // frames per block in plan and scan
+
+// the aligned dword at x (bytes past the buffer read as 0: its last, partial dword by bytes)
+__device__ __forceinline__ uint32_t ldw(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t x) {
+    if (__builtin_expect(x + 4u <= fb, 1))
+        return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)x, 0, 0);
+    return gbyte(rs, x) | (gbyte(rs, x + 1u) << 8) | (gbyte(rs, x + 2u) << 16) |
+           (gbyte(rs, x + 3u) << 24);
+}
+
+// big-endian RFC 1071 sum (folded) of buffer bytes [a, b), one lane: headers, addresses
+__device__ __forceinline__ uint32_t range_be_sum(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 uint32_t a, uint32_t b) {
+    if (b <= a) return 0u;
+    uint32_t acc = 0;
+    for (uint32_t x = a & ~3u; x < b; x += 4u) {
+        const uint32_t lo = a > x ? a - x : 0u, hi = b - x < 4u ? b - x : 4u;
+        acc = hsum(ldw(rs, fb, x) & byte_mask((int)lo, (int)hi), acc);
+    }
+    return be_sum(acc, a);
+}
+
+// The records of the wave's tile [p0, p0 + 64) of n, coalesced: 5 dwordx4 per lane over its
+// contiguous 5 KiB into the stage `st` (64 * 21 dwords: record r at stride 21 dwords), as
+// rpkt_tx.hip's load_records_tile
+__device__ __forceinline__ void stage_records_tile(uint32_t* st, const rpkt_rec_t* __restrict__ recs,
+                                                   uint32_t p0, uint32_t n, int lane) {
+    const uint32_t nrec = n - p0 < (uint32_t)kWave ? n - p0 : (uint32_t)kWave;
+    const u32x4* in = reinterpret_cast<const u32x4*>(recs + p0);
+    u32x4 v[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const uint32_t c = k * kWave + lane;
+        v[k] = c / 5 < nrec ? __builtin_nontemporal_load(&in[c]) : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const uint32_t c = k * kWave + lane;
+        uint32_t* d = st + (c / 5) * 21 + (c % 5) * 4;
+        d[0] = v[k].x;
+        d[1] = v[k].y;
+        d[2] = v[k].z;
+        d[3] = v[k].w;
+    }
+    wave_sync();
+}
+
+// 64-bit inclusive scan over the wave
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x, int lane) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint64_t y = __shfl_up((unsigned long long)x, d, kWave);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+
+// Exclusive scan of (a, b) over the block's kSegBlock threads; tot_*: the block's sums.
+// red: 4 * kWavesPerBlock u64 of LDS.
+__device__ __forceinline__ void block_excl_scan2(uint64_t& a, uint64_t& b, uint64_t& tot_a,
+                                                 uint64_t& tot_b, uint64_t* red) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint64_t ia = wave_incl_scan64(a, lane), ib = wave_incl_scan64(b, lane);
+    if (lane == kWave - 1) {
+        red[2 * wave] = ia;
+        red[2 * wave + 1] = ib;
+    }
+    __syncthreads();
+    uint64_t ba = 0, bb = 0;
+    tot_a = tot_b = 0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) {
+        if (w < wave) {
+            ba += red[2 * w];
+            bb += red[2 * w + 1];
+        }
+        tot_a += red[2 * w];
+        tot_b += red[2 * w + 1];
+    }
+    __syncthreads();                                   // red is free for the next call
+    a = ba + ia - a;
+    b = bb + ib - b;
+}
+
+// bytes [lo, hi) of dword v to the output at x (4-B aligned): one dword store, or bytes
+__device__ __forceinline__ void store_dword_part(__amdgpu_buffer_rsrc_t ro, uint32_t x, uint32_t v,
+                                                 int lo, int hi) {
+    if (hi <= 0 || lo >= 4) return;
+    if (lo <= 0 && hi >= 4) {
+        __builtin_amdgcn_raw_buffer_store_b32(v, ro, (int)x, 0, 0);
+        return;
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (b >= lo && b < hi)
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(v >> (8 * b)), ro, (int)(x + b), 0, 0);
+}
+
+// Copy src [s0, s0 + len) of the frames buffer to dst [d0, d0 + len) of the output, the
+// whole wave: lane l of pass t owns the 16-B aligned destination chunk t * 64 + l.  The
+// chunk's source bytes start at phase sh = (s0 - d0) & 15 of an aligned source chunk
+// (wave-uniform), so they are that chunk and the next, shifted.  Whole chunks go out as one
+// dwordx4 store, the (at most two) partial ones as dwords and bytes: their other bytes belong
+// to the neighbouring output frames, which other waves write.  Returns this lane's part of
+// the word sum of the bytes copied, over absolute-destination-aligned LE words (SUM).
+constexpr int kCopyUnroll = 2;     // destination chunks (and their loads) in flight per lane
+#ifndef RPKT_SEG_NT
+#define RPKT_SEG_NT 0              // 2: non-temporal copy loads and dwordx4 stores
+#endif
+constexpr int kCopyAux = RPKT_SEG_NT;
+template <bool SUM>
+__device__ __forceinline__ uint32_t wave_copy(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                              __amdgpu_buffer_rsrc_t ro, uint32_t s0, uint32_t d0,
+                                              uint32_t len, int lane) {
+    uint32_t acc = 0;
+    if (len == 0) return acc;
+    const uint32_t dbase = d0 & ~15u, dend = d0 + len;
+    const uint32_t sh = (s0 - d0) & 15u, q = sh >> 2, r = sh & 3u;       // wave-uniform
+    const uint32_t nchunk = (dend - dbase + 15u) >> 4;                   // counted: dc never wraps
+    for (uint32_t c0 = (uint32_t)lane; c0 < nchunk; c0 += kCopyUnroll * kWave) {
+        u32x4 A[kCopyUnroll], B[kCopyUnroll];
+        uint32_t sa[kCopyUnroll];
+        // every load of the pass first, unconditional (a chunk past the end reads the
+        // descriptor's out-of-range offset: zeros, no traffic)
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; ++u) {
+            const uint32_t c = c0 + u * kWave;
+            // source address of destination byte dc (before the frame's start for the first
+            // chunk: those addresses wrap past the range and read as 0; their bytes are not
+            // kept)
+            sa[u] = c < nchunk ? (s0 + (dbase + 16u * c - d0)) & ~15u : fb;
+            A[u] = load16_fast<kCopyAux>(rs, sa[u]);
+            B[u] = load16_fast<kCopyAux>(rs, sh != 0u && c < nchunk ? sa[u] + 16u : fb);
+        }
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; ++u) {
+            const uint32_t c = c0 + u * kWave;
+            if (c >= nchunk) break;
+            const uint32_t dc = dbase + 16u * c;
+            u32x4 a = A[u], b = B[u];
+            // a chunk that straddles the buffer's end was dropped whole: re-read it (rare)
+            if (__builtin_expect(straddles(sa[u], fb), 0)) a = load16(rs, sa[u], fb);
+            if (__builtin_expect(sh != 0u && straddles(sa[u] + 16u, fb), 0))
+                b = load16(rs, sa[u] + 16u, fb);
+            const uint32_t W[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            uint32_t T[5];
+#pragma unroll
+            for (int m = 0; m < 5; ++m)
+                T[m] = q == 0u ? W[m] : (q == 1u ? W[m + 1] : (q == 2u ? W[m + 2] : W[m + 3]));
+            u32x4 v;
+            v.x = align_bytes(T[1], T[0], r);
+            v.y = align_bytes(T[2], T[1], r);
+            v.z = align_bytes(T[3], T[2], r);
+            v.w = align_bytes(T[4], T[3], r);
+            const int lo = dc < d0 ? (int)(d0 - dc) : 0;
+            const int hi = dend - dc < 16u ? (int)(dend - dc) : 16;
+            if (SUM) acc += chunk_sum(v, lo, hi);
+            if (lo == 0 && hi == 16) {
+                __builtin_amdgcn_raw_buffer_store_b128(v, ro, (int)dc, 0, kCopyAux);
+            } else {
+                store_dword_part(ro, dc, v.x, lo, hi);
+                store_dword_part(ro, dc + 4u, v.y, lo - 4, hi - 4);
+                store_dword_part(ro, dc + 8u, v.z, lo - 8, hi - 8);
+                store_dword_part(ro, dc + 12u, v.w, lo - 12, hi - 12);
+            }
+        }
+    }
+    return acc;
+}
+
+// the fields an output's header differs in: n bytes at frame offset off, value in memory order
+struct SegPatch {
+    uint32_t off, n, val;
+};
+constexpr int kSegPatches = 5;
+
+// The header [s0, s0 + len) goes to [d0, d0 + len) a lane per 4-B aligned destination dword
+// (headers are a few dwords: one pass as a rule).  header_dword: the source bytes of
+// destination dword c.
+__device__ __forceinline__ uint32_t header_dword(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 uint32_t s0, uint32_t d0, uint32_t c) {
+    return gdword(rs, fb, s0 + ((d0 & ~3u) + 4u * c - d0));
+}
+
+// Copy the header with the patches applied.  `first`: header_dword of this lane's first
+// dword (c = lane), which the caller loaded along with the payload.
+__device__ __forceinline__ void wave_copy_header(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 __amdgpu_buffer_rsrc_t ro, uint32_t s0,
+                                                 uint32_t d0, uint32_t len, uint32_t first,
+                                                 const SegPatch (&P)[kSegPatches], int lane) {
+    const uint32_t dend = d0 + len;
+    const uint32_t ndw = (dend - (d0 & ~3u) + 3u) >> 2;
+    for (uint32_t c = (uint32_t)lane; c < ndw; c += kWave) {
+        const uint32_t dd = (d0 & ~3u) + 4u * c;
+        const int rel = (int)(dd - d0);                 // header offset of the dword's byte 0
+        uint32_t v = c < (uint32_t)kWave ? first : header_dword(rs, fb, s0, d0, c);
+#pragma unroll
+        for (int k = 0; k < kSegPatches; ++k) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t idx = (uint32_t)(rel + b) - P[k].off;
+                if (idx < P[k].n)
+                    v = (v & ~(0xffu << (8 * b))) | (((P[k].val >> (8u * idx)) & 0xffu) << (8 * b));
+            }
+        }
+        store_dword_part(ro, dd, v, rel < 0 ? -rel : 0, dend - dd < 4u ? (int)(dend - dd) : 4);
+    }
+}
+
+}  // namespace

@@ -83,7 +83,10 @@ ABI = {
     "rpkt_gpu_segment_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_segment_batch": (_i, [_B, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
                                     _p]),
-    "rpkt_gpu_options_batch": (_i, [_B, _p, _p, _p]),
+    "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
+                                     _p, _p, _p]),
+    "rpkt_gpu_options_batch":(_i, [_B, _p, _p, _p]),
     "rpkt_gpu_options_batch_compact": (_i, [_B, _p, _p, _p]),
     "rpkt_gpu_parse_options_batch": (_i, [_B, _u32, _p, _p, _p, _u32, _p]),
     "rpkt_gpu_parse_options_batch_compact": (_i, [_B, _u32, _p, _p, _p, _u32, _p]),
@@ -624,6 +627,69 @@ def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=N
           out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, seg_first.data_ptr(),
           totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
     return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
+
+
+COALESCE_TRUST_SUMS = 1
+
+
+def coalesce_workspace(n, device="cuda"):
+    """The workspace tensor of coalesce_batch for n positions
+    (rpkt_gpu_coalesce_workspace_bytes)."""
+    return _bytes(max(int(lib().rpkt_gpu_coalesce_workspace_bytes(n)), 16), 1, device)
+
+
+def coalesce_batch(batch, recs, order=None, max_payload=65535, trust_sums=False, out_frames=None,
+                   out_offsets=None, out_cap=None, out_bytes=None, src_first=None, out_mss=None,
+                   totals=None, workspace=None, stream=None):
+    """rpkt_gpu_coalesce_batch: TCP receive coalescing (GRO) of `batch`, located by `recs`
+    (parse_batch's records of this batch, with both sums unless trust_sums), the positions
+    taken in `order` (an int32 tensor of n frame indices, e.g. flow_order's; None: frame
+    order).  Returns (out, src_first, totals): `out` a packed DeviceBatch over out_cap slots
+    (slots past totals[0] are empty frames), src_first an int32 tensor of n + 1 (output j is
+    made of positions [src_first[j], src_first[j + 1])), totals an int64 tensor {n_out,
+    out_bytes_needed}.  out_mss (optional, an int16 tensor of n) receives each merged output's
+    segment size.  Nothing here reads the device: when totals exceeds out_cap / out_bytes the
+    batch overflowed and `out` is unspecified.  By default the outputs are sized from the
+    documented bound: out_cap = n slots and out_bytes = frames_bytes (without an order; with one
+    give out_bytes when it repeats frames)."""
+    torch = _torch()
+    dev = batch.frames.device
+    n, fbytes = batch.n, batch.frames.numel()
+    if out_cap is None:
+        out_cap = out_offsets.numel() - 1 if out_offsets is not None else max(n, 1)
+    if out_bytes is None:
+        out_bytes = out_frames.numel() if out_frames is not None else fbytes
+    if out_frames is None:
+        out_frames = _bytes(max(out_bytes, 16), 1, dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(out_cap + 1, dtype=torch.int32, device=dev)
+    if out_frames.numel() < out_bytes or out_offsets.numel() < out_cap + 1:
+        raise RpktError("coalesce_batch: outputs smaller than out_bytes / out_cap + 1")
+    src_first = torch.empty(n + 1, dtype=torch.int32, device=dev) if src_first is None else src_first
+    totals = torch.empty(2, dtype=torch.int64, device=dev) if totals is None else totals
+    workspace = coalesce_workspace(n, dev) if workspace is None else workspace
+    if recs.numel() != n * REC_BYTES or src_first.numel() < n + 1:
+        raise RpktError("coalesce_batch: records or src_first do not fit %d frames" % n)
+    if order is not None and (order.numel() < n or order.element_size() != 4):
+        raise RpktError("coalesce_batch: order takes %d 32-bit entries" % n)
+    if out_mss is not None and (out_mss.numel() < n or out_mss.element_size() != 2):
+        raise RpktError("coalesce_batch: out_mss takes %d 16-bit entries" % n)
+    _call("rpkt_gpu_coalesce_batch", ctypes.byref(batch.desc()), recs.data_ptr(), _ptr(order),
+          max_payload, COALESCE_TRUST_SUMS if trust_sums else 0, out_frames.data_ptr(), out_bytes,
+          out_offsets.data_ptr(), out_cap, src_first.data_ptr(), _ptr(out_mss), totals.data_ptr(),
+          workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), src_first, totals
+
+
+def flow_order(flow_ev):
+    """The order that brings each flow's frames together for coalesce_batch: the stable
+    argsort of the flow events' bucket field (bits 32..47), the u32 indices in an int32 tensor
+    (as every index tensor of this module) on flow_ev's device (CPU or GPU).  Frames of one
+    flow keep their arrival order; two flows that share a bucket merely stay interleaved and
+    merge less."""
+    import torch
+    bucket = (flow_ev >> 32) & 0xffff
+    return torch.sort(bucket, stable=True)[1].to(torch.int32)
 
 
 def options_batch(batch, recs, opts=None, stream=None, compact=False):

@@ -1,0 +1,158 @@
+"""Time rpkt_gpu_coalesce_batch against a device-to-device copy of the same bytes and against
+rpkt_gpu_segment_batch on the forward workload, all in one run (GPU box):
+
+    python tools/coalesce_time.py [--out profiles/coalesce/times.json]
+
+Workload: the inverse of tools/segment_time.py's.  Its 32,768 Ether/IPv4/TCP super-frames of
+54 + 32,768 B are cut on the device at mss 1448 by rpkt_gpu_segment_batch into 753,664 segments
+(54 + 1448 B, the last of each frame 54 + 912 B), parsed with both sums, and coalesced back into
+32,768 frames: about 1.13 GB in and 1.07 GB out, past the 256-MB Infinity Cache.  Two such
+batches (two seeds) are rotated.
+
+Timed as tools/segment_time.py times its legs: warm-up launches for at least 0.3 s, then two
+HIP events on the launch stream around LAUNCHES back-to-back calls (default 50), the three legs
+in interleaved rounds (the first round thrown away; the figure is the median of the others).
+The copy is torch's Tensor.copy_ of the coalescing's input frames.  Fractions are of 8 TB/s.
+
+The split of the time between the eight kernels comes from a run of its own:
+
+    rocprofv3 --kernel-trace --stats -d DIR -o co -- python tools/coalesce_time.py --trace-launches 6
+
+The run also checks the output: 23 segments an output, every output the source super-frame
+byte for byte (but its TCP checksum field, which the source leaves 0), and a parse of the
+output with both sums finds every frame OK with valid IPv4 and TCP sums."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from segment_time import HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, super_frames  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/coalesce/times.json")
+    ap.add_argument("--n", type=int, default=32768)
+    ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--trace-launches", type=int, default=0,
+                    help="no timing: this many calls, for a kernel-trace or counter pass")
+    a = ap.parse_args()
+    import time
+
+    import torch
+    from rpkt_amd import engine
+    from rpkt_amd.records import as_records
+
+    stream = torch.cuda.current_stream()
+    n, flen = a.n, HDR + PAYLOAD
+    per = -(-PAYLOAD // MSS)
+    n_seg, seg_bytes = n * per, n * (per * HDR + PAYLOAD)
+    srcs, srecs, segs, recs = [], [], [], []
+    for seed in (31, 3131):
+        db = engine.DeviceBatch(torch.from_numpy(super_frames(n, seed).reshape(-1)).to("cuda"), n,
+                                stride=flen)
+        srcs.append(db)
+        srecs.append(engine.parse_batch(db, 0))
+        sdb, _, tot = engine.segment_batch(db, srecs[-1], MSS, out_cap=n_seg, out_bytes=seg_bytes)
+        assert tot.cpu().tolist() == [n_seg, seg_bytes]
+        segs.append(sdb)
+        recs.append(engine.parse_batch(sdb, 3))
+    R = len(segs)
+    out_frames = torch.empty(max(n * flen, seg_bytes), dtype=torch.uint8, device="cuda")
+    out_offsets = torch.empty(n_seg + 1, dtype=torch.int32, device="cuda")
+    first = torch.empty(n_seg + 1, dtype=torch.int32, device="cuda")
+    out_mss = torch.empty(n_seg, dtype=torch.int16, device="cuda")
+    totals = torch.zeros(2, dtype=torch.int64, device="cuda")
+    ws = engine.coalesce_workspace(n_seg)
+    sws = engine.segment_workspace(n)
+
+    def coalesce(k):
+        engine.coalesce_batch(segs[k % R], recs[k % R], out_frames=out_frames, out_offsets=out_offsets,
+                              out_cap=n, out_bytes=n * flen, src_first=first, out_mss=out_mss,
+                              totals=totals, workspace=ws, stream=stream)
+
+    def copy(k):
+        out_frames[:seg_bytes].copy_(segs[k % R].frames[:seg_bytes])
+
+    def segment(k):
+        engine.segment_batch(srcs[k % R], srecs[k % R], MSS, out_frames=out_frames,
+                             out_offsets=out_offsets, out_cap=n_seg, out_bytes=seg_bytes,
+                             seg_first=first, totals=totals, workspace=sws, stream=stream)
+
+    if a.trace_launches:
+        for k in range(a.trace_launches):
+            coalesce(k)
+        torch.cuda.synchronize()
+        return
+    legs = {"coalesce_batch": coalesce, "device_copy": copy, "segment_batch": segment}
+    k, t_w = 0, time.perf_counter()
+    while k < 8 or time.perf_counter() - t_w < 0.3:
+        for fn in legs.values():
+            fn(k)
+        k += 1
+        if k % 8 == 0:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for r in range(a.rounds + 1):
+        for name, fn in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for j in range(a.launches):
+                fn(j)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if r:
+                ms[name].append(e0.elapsed_time(e1) / a.launches)
+    med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+
+    # the output is the source (checked on both batches)
+    for k in range(R):
+        out_frames.fill_(0xa5)
+        coalesce(k)
+        torch.cuda.synchronize()
+        assert totals.cpu().tolist() == [n, n * flen], totals.cpu().tolist()
+        sf = first.cpu().numpy().view(np.uint32)
+        assert np.array_equal(sf[:n + 1], np.arange(n + 1, dtype=np.uint32) * per)
+        assert (out_mss[:n] == MSS).all().item()
+        got = out_frames[:n * flen].view(n, flen)
+        src = srcs[k].frames.view(n, flen)
+        assert torch.equal(got[:, :50], src[:, :50]) and torch.equal(got[:, 52:], src[:, 52:])
+        odb = engine.DeviceBatch(out_frames, n, out_offsets)
+        orec = as_records(engine.parse_batch(odb, 3).cpu().numpy())
+        assert (orec["status"] == 0).all() and (orec["ip_sum"] == 0xffff).all()
+        assert (orec["l4_sum"] == 0xffff).all() and (orec["payload_len"] == PAYLOAD).all()
+
+    moved = {"frames_in": seg_bytes, "records_in": n_seg * 80, "offsets_in": (n_seg + 1) * 4,
+             "frames_out": n * flen, "offsets_out": (n + 1) * 4, "src_first_out": (n_seg + 1) * 4,
+             "out_mss_out": n_seg * 2}
+    alg = sum(moved.values())
+    seg_alg = n * flen + n * 80 + seg_bytes + (n_seg + 1) * 4       # tools/segment_time.py's count
+    res = {"device": engine.device_info(), "build": engine.lib().rpkt_gpu_build_info().decode(),
+           "segments": n_seg, "frames": n, "frame_len": flen, "mss": MSS, "bytes": moved,
+           "batches_rotated": R, "launches_per_round": a.launches, "rounds": a.rounds, "ms": {}}
+    for name, v in med.items():
+        res["ms"][name] = {"ms": round(v, 4), "rounds_ms": [round(x, 4) for x in ms[name]]}
+    for name, b in (("coalesce_batch", alg), ("device_copy", 2 * seg_bytes), ("segment_batch", seg_alg)):
+        res["ms"][name]["bytes"] = b
+        res["ms"][name]["fraction_of_8TBs"] = round(b / (med[name] * 1e-3) / HBM_BYTES_PER_S, 4)
+    per_byte = {name: med[name] / res["ms"][name]["bytes"] for name in legs}
+    res["coalesce_over_copy_per_byte"] = round(per_byte["coalesce_batch"] / per_byte["device_copy"], 4)
+    res["segment_over_copy_per_byte"] = round(per_byte["segment_batch"] / per_byte["device_copy"], 4)
+    res["coalesce_over_segment_per_byte"] = round(
+        per_byte["coalesce_batch"] / per_byte["segment_batch"], 4)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
