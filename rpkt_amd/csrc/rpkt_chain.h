@@ -1,8 +1,8 @@
 // rpkt_chain.h — device code of the parse over rpkt-dpdk's Pbuf (mbuf chains), shared by
 // rpkt_parse.hip (rpkt_gpu_parse_chains) and rpkt_tunnel_chains.hip
-// (rpkt_gpu_parse_tunnel_chains): the segment source, chunk() at a logical cursor, the
-// dword reader over segment 0's window, the lane-per-chain parse and the flattened
-// (chain, segment) checksum stream.
+// (rpkt_gpu_parse_tunnel_chains): the segment source, ChainView (the chain model of
+// rpkt_common.h's view concept: chunk() at a logical cursor, the dword reader over segment
+// 0's window), the lane-per-chain parse and the flattened (chain, segment) checksum stream.
 #pragma once
 #include "rpkt_common.h"
 
@@ -75,72 +75,39 @@ struct ChainDw {
     }
 };
 
-// parse_ip6 (rpkt_common.h) over a Pbuf: every header size against chunk().len() at its
-// first byte (the rest of the segment holding it, cut at the packet end), the payload
-// length against remaining() (ipv6/generated.rs:40-92 and the extension headers'
-// parses, as oracle/rpkt_oracle_chain.c parse_pbuf_ip6).
-__device__ __forceinline__ uint32_t parse_chain_ip6(const ChainDw& dw, uint32_t C, uint32_t pkt,
-                                                    const ChainSrc& S, uint32_t a, uint32_t b,
-                                                    uint32_t l3, uint32_t* w, uint32_t& l4,
-                                                    uint32_t& l4rem, uint32_t& proto,
-                                                    uint32_t& paddr) {
-    // chunk at logical cursor c under the packet end `lim`, its first byte's address
-    auto chunk = [&](uint32_t c, uint32_t lim, uint32_t& abs) -> uint32_t {
+// The lane's chain as a Pbuf: the chain model of the view concept (rpkt_common.h).  chunk()
+// at logical cursor c under the packet end lim (the trim of the views above it): below
+// segment 0's end C the rest of segment 0; past it chain_chunk walks the segments (empty
+// ones skipped, as advance_common).  at = the absolute address of the chunk's first byte
+// (fb, where every load returns 0, when the chunk is empty); d reads there.
+struct ChainView {
+    ChainSrc S;
+    uint32_t a, b, C;
+    ChainDw d;
+    __device__ __forceinline__ uint32_t chunk(uint32_t c, uint32_t lim, uint32_t& at) const {
+        at = S.fb;
+        if (c >= lim) return 0u;
         if (c < C) {
-            abs = dw.off0 + c;
+            at = d.off0 + c;
             return (C < lim ? C : lim) - c;
         }
-        abs = S.fb;
-        return c < lim ? chain_chunk(S, a, b, c, lim, abs) : 0u;
-    };
-    uint32_t ab3;
-    if (chunk(l3, pkt, ab3) < 40u) return RPKT_S_IP6_SHORT;               // :42
-    uint32_t F[10];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) F[k] = dw(ab3 + 4u * k);
-    const uint32_t plen = be16_lo(F[1]);
-    if (plen + 40u > pkt - l3) return RPKT_S_IP6_BAD_LEN;                 // :47
-    w[6] = bswap32(F[0]);
-    w[7] = plen | (F[1] & 0xffff0000u);
-    w[9] = bswap32(F[2]) ^ bswap32(F[3]) ^ bswap32(F[4]) ^ bswap32(F[5]);
-    w[10] = bswap32(F[6]) ^ bswap32(F[7]) ^ bswap32(F[8]) ^ bswap32(F[9]);
-    const uint32_t src_sum = addr_words_sum(F[2], F[3], F[4], F[5]);
-    uint32_t pdst_sum = addr_words_sum(F[6], F[7], F[8], F[9]);
-    uint32_t pdst_off = l3 + 24u;
-    uint32_t c = l3 + 40u;
-    const uint32_t end = c + plen;                                        // payload() trim
-    uint32_t nh = (F[1] >> 16) & 0xffu, n_ext = 0, status = RPKT_S_OK;
-    for (int k = 0; k < RPKT_MAX_IP6_EXT && is_ip6_ext(nh); ++k) {
-        const bool fg = nh == 44u, ah = nh == 51u, rt = nh == 43u;
-        const uint32_t fixed = (nh == 0u || nh == 60u) ? 2u : (ah ? 12u : 8u);
-        uint32_t ax;
-        const uint32_t cl = chunk(c, end, ax);
-        if (cl < fixed) { status = RPKT_S_IP6_EXT_SHORT; break; }
-        const uint32_t d0 = dw(ax);
-        const uint32_t b1 = (d0 >> 8) & 0xffu;
-        const uint32_t hl = fg ? 8u : (ah ? b1 * 4u + 8u : b1 * 8u + 8u);
-        if (!fg && (hl < fixed || hl > cl)) { status = RPKT_S_IP6_EXT_BAD_LEN; break; }
-        if (rt && (d0 >> 24) != 0u) {
-            const uint32_t type = (d0 >> 16) & 0xffu, n_addr = (hl - 8u) >> 4;
-            if (n_addr != 0u && (type == 0u || type == 2u || type == 4u)) {
-                const uint32_t r = 8u + (type == 4u ? 0u : 16u * (n_addr - 1u));
-                pdst_off = c + r;
-                pdst_sum = addr_words_sum(dw(ax + r), dw(ax + r + 4u), dw(ax + r + 8u),
-                                          dw(ax + r + 12u));
-            }
-        }
-        nh = d0 & 0xffu;
-        c += hl;
-        n_ext += 1u;
-        if (fg && (be16_hi(d0) & 0xfff9u) != 0u) { status = RPKT_S_IP6_FRAGMENT; break; }
+        return chain_chunk(S, a, b, c, lim, at);
     }
-    if (status == RPKT_S_OK && is_ip6_ext(nh)) status = RPKT_S_L4_OTHER;
-    w[8] = n_ext | (nh << 8) | (pdst_off << 16);
-    l4 = c;
-    l4rem = end - c;
-    proto = nh;
-    paddr = src_sum + pdst_sum;
-    return status;
+    __device__ __forceinline__ uint32_t dw(uint32_t at) const { return d(at); }
+    template <int N>
+    __device__ __forceinline__ void read_words(uint32_t at, uint32_t (&F)[N]) const {
+#pragma unroll
+        for (int k = 0; k < N; ++k) F[k] = d(at + 4u * k);
+    }
+};
+
+// The view of the lane's chain [a, b) whose segment 0 (s0) is in the lane's window slot.
+__device__ __forceinline__ ChainView chain_view(const WaveScratch& W, int lane, Frame s0,
+                                                const ChainSrc& S, uint32_t a, uint32_t b,
+                                                __amdgpu_buffer_rsrc_t rs) {
+    const uint32_t ph = s0.off & 15u, wl = (uint32_t)kWin - ph;
+    return ChainView{S, a, b, s0.len,
+                     ChainDw{&W.win[lane * kSlot], ph, s0.off, s0.len < wl ? s0.len : wl, rs}};
 }
 
 // Lane-per-chain parse: parse_lane with the chunk/remaining distinction of a Pbuf.
@@ -217,9 +184,8 @@ __device__ __forceinline__ void parse_chain_lane(const WaveScratch& W, int lane,
     uint32_t l4, limit, l4rem, proto, paddr;
     if (v6) {
         L.is6 = true;
-        const uint32_t wl = (uint32_t)kWin - ph;
-        const ChainDw dw{slot, ph, s0.off, C < wl ? C : wl, rs};
-        status = parse_chain_ip6(dw, C, pkt, S, a, b, l3, w, l4, l4rem, proto, paddr);
+        status = parse_ip6(chain_view(W, lane, s0, S, a, b, rs), l3, pkt, w, l4, l4rem, proto,
+                           paddr);
         if (status != RPKT_S_IP6_SHORT && status != RPKT_S_IP6_BAD_LEN) {
             w[16] |= l4 << 16;
             w[17] = (l4 & 0xffffu) | (l4rem << 16);
@@ -231,51 +197,39 @@ __device__ __forceinline__ void parse_chain_lane(const WaveScratch& W, int lane,
         }
         limit = l4 + l4rem;
     } else {
-    // Ipv4::parse (ipv4/generated.rs:35-51): chunk vs remaining
-    Hdr6 ip;
-    uint32_t ck3 = 0, ab3 = 0;
-    const bool fast3 = l3 < C;
-    if (fast3) {
-        ck3 = C - l3;
-        read_hdr(slot, ph + l3, ip);
-    } else {
-        if (l3 < pkt) ck3 = chain_chunk(S, a, b, l3, pkt, ab3);
-        gread20(rs, S.fb, ck3 ? ab3 : S.fb, ip.F);
-    }
-    const uint32_t vhl = ip.F[0] & 0xffu;
-    const uint32_t ihl4 = (vhl & 0xfu) * 4u;
-    const uint32_t tot = be16_hi(ip.F[0]);
-    if (ck3 < 20) status = RPKT_S_IP_SHORT;
-    else if (ihl4 < 20) status = RPKT_S_IP_BAD_IHL;
-    else if (ihl4 > ck3) status = RPKT_S_IP_IHL_GT_LEN;
-    else if (tot < ihl4) status = RPKT_S_IP_TOT_LT_IHL;
-    else if (tot > pkt - l3) status = RPKT_S_IP_TOT_GT_LEN;
-    if (status != RPKT_S_OK) {
-        w[0] |= status;
-        L.status = status;
-        return;
-    }
-    proto = (ip.F[2] >> 8) & 0xffu;
-    const uint32_t src = bswap32(ip.F[3]), dst = bswap32(ip.F[4]);
-    w[6] = (ip.F[0] & 0xffffu) | (tot << 16);
-    w[7] = be16_lo(ip.F[1]) | (be16_hi(ip.F[1]) << 16);
-    w[8] = (ip.F[2] & 0xffffu) | (be16_hi(ip.F[2]) << 16);
-    w[9] = src;
-    w[10] = dst;
-    if (flags & RPKT_F_IP_SUM)
-        w[18] = fast3 ? be_sum(raw_range_sum(slot, ip.R, ip.a0, ph + l3, ph + l3 + ihl4),
-                               s0.off + l3)
-                      : gsum_be(rs, ab3, ihl4);
-    l4 = l3 + ihl4;                                            // Ipv4::payload :115-127
-    limit = l3 + tot;
-    l4rem = tot - ihl4;
-    w[16] |= l4 << 16;
-    w[17] = l4 | (l4rem << 16);
-    paddr = (src >> 16) + (src & 0xffffu) + (dst >> 16) + (dst & 0xffffu);
+        // Ipv4::parse (ip4_rules): chunk vs remaining
+        Hdr6 ip;
+        uint32_t ck3 = 0, ab3 = 0;
+        const bool fast3 = l3 < C;
+        if (fast3) {
+            ck3 = C - l3;
+            read_hdr(slot, ph + l3, ip);
+        } else {
+            if (l3 < pkt) ck3 = chain_chunk(S, a, b, l3, pkt, ab3);
+            gread20(rs, S.fb, ck3 ? ab3 : S.fb, ip.F);
+        }
+        const Ip4Out o = ip4_rules(ip.F, ck3, pkt - l3, w);
+        status = o.status;
+        if (status != RPKT_S_OK) {
+            w[0] |= status;
+            L.status = status;
+            return;
+        }
+        if (flags & RPKT_F_IP_SUM)
+            w[18] = fast3 ? be_sum(raw_range_sum(slot, ip.R, ip.a0, ph + l3, ph + l3 + o.ihl4),
+                                   s0.off + l3)
+                          : gsum_be(rs, ab3, o.ihl4);
+        l4 = l3 + o.ihl4;                                      // Ipv4::payload :115-127
+        limit = l3 + o.tot;
+        l4rem = o.tot - o.ihl4;
+        w[16] |= l4 << 16;
+        w[17] = l4 | (l4rem << 16);
+        proto = o.proto;
+        paddr = o.paddr;
     }
 
-    // Udp::parse / Tcp::parse against the chunk at l4 under the trimmed end (an IPv6 L4
-    // header past segment 0's window is read from global memory)
+    // Udp::parse / Tcp::parse (l4_rules) against the chunk at l4 under the trimmed end (an
+    // IPv6 L4 header past segment 0's window is read from global memory)
     Hdr6 h4;
     uint32_t ck4 = 0, ab4 = 0;
     const bool fast4 = l4 < C && ph + l4 + 20u <= (uint32_t)kWin;
@@ -286,44 +240,10 @@ __device__ __forceinline__ void parse_chain_lane(const WaveScratch& W, int lane,
         if (l4 < limit) ck4 = chain_chunk(S, a, b, l4, limit, ab4);
         gread20(rs, S.fb, ck4 ? ab4 : S.fb, h4.F);
     }
-    uint32_t l4len = 0;
-    bool other_sum = false;                                    // ICMP / GRE (parse_lane)
-    if (proto == 17u) {
-        const uint32_t ulen = be16_lo(h4.F[1]);
-        if (ck4 < 8) status = RPKT_S_UDP_SHORT;
-        else if (ulen < 8 || ulen > l4rem) status = RPKT_S_UDP_BAD_LEN;
-        else {
-            w[11] = be16_lo(h4.F[0]) | (be16_hi(h4.F[0]) << 16);
-            w[14] = ulen;
-            w[15] = be16_hi(h4.F[1]);
-            w[17] = ((l4 + 8) & 0xffffu) | ((ulen - 8) << 16);
-            l4len = ulen;
-        }
-    } else if (proto == 6u) {
-        const uint32_t hl = ((h4.F[3] >> 4) & 0xfu) * 4u;
-        if (ck4 < 20) status = RPKT_S_TCP_SHORT;
-        else if (hl < 20 || hl > ck4) status = RPKT_S_TCP_BAD_DOFF;
-        else {
-            w[11] = be16_lo(h4.F[0]) | (be16_hi(h4.F[0]) << 16);
-            w[12] = bswap32(h4.F[1]);
-            w[13] = bswap32(h4.F[2]);
-            w[14] = be16_lo(h4.F[3]) | (be16_hi(h4.F[3]) << 16);
-            w[15] = be16_lo(h4.F[4]) | (be16_hi(h4.F[4]) << 16);
-            w[17] = ((l4 + hl) & 0xffffu) | ((l4rem - hl) << 16);
-            l4len = l4rem;
-        }
-    } else {
-        // ICMP and GRE-with-checksum sums over the IP payload, as parse_lane (the GRE
-        // header's first byte is the first byte of the chunk at l4)
-        status = RPKT_S_L4_OTHER;
-        if (!v6 && proto == 1u) {
-            if (l4rem == 0u) status = RPKT_S_ICMP_EMPTY;
-            else other_sum = true;
-        } else if (proto == 47u && l4rem >= 4u && (h4.F[0] & 0x80u)) {
-            other_sum = true;
-        }
-        l4len = l4rem;
-    }
+    const L4Out r4 = l4_rules(h4.F, ck4, l4rem, proto, v6, l4, w);
+    status = r4.status;
+    const uint32_t l4len = r4.l4len;
+    const bool other_sum = r4.other_sum;
     w[0] |= status;
     L.status = status;
     if ((status == RPKT_S_OK || other_sum) && (flags & RPKT_F_L4_SUM)) {

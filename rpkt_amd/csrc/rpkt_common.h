@@ -782,6 +782,38 @@ struct FrameDw {
     }
 };
 
+// ---- byte access of the header rules: one concept, two models ----
+// A view is one lane's packet as the reference's buffer traits show it, with cursors as
+// logical positions in the packet:
+//   chunk(c, lim, at)     chunk().len() at cursor c under the packet end lim (the trim of
+//                         the layers above): the contiguous bytes a header-size test sees,
+//                         and `at`, the token of the chunk's first byte for the readers.
+//                         remaining() is lim - c: what a total-length test sees;
+//   dw(at)                bytes at .. at + 3 as a little-endian dword;
+//   read_words<N>(at, F)  the N dwords of a header that was tested to lie in the chunk.
+// Every rule stated over a view (parse_ip6 below, decode_tunnel in rpkt_tunnel.h) holds for
+// both models: FlatView, a flat frame, where the chunk is all that remains and `at` is the
+// frame offset; ChainView (rpkt_chain.h), an mbuf chain, where the chunk ends with the
+// segment and `at` is an absolute address.
+struct FlatView {
+    FrameDw f;
+    __device__ __forceinline__ uint32_t chunk(uint32_t c, uint32_t lim, uint32_t& at) const {
+        at = c;
+        return c < lim ? lim - c : 0u;
+    }
+    __device__ __forceinline__ uint32_t dw(uint32_t at) const { return f(at); }
+    // a header inside the LDS window: its N + 1 aligned dwords in one round
+    template <int N>
+    __device__ __forceinline__ void read_words(uint32_t at, uint32_t (&F)[N]) const {
+        const uint32_t x = f.ph + at, a0 = x & ~3u, sh = x & 3u;
+        uint32_t R[N + 1];
+#pragma unroll
+        for (int k = 0; k < N + 1; ++k) R[k] = lds32(f.slot, a0 + 4 * k);
+#pragma unroll
+        for (int k = 0; k < N; ++k) F[k] = align_bytes(R[k + 1], R[k], sh);
+    }
+};
+
 // RFC 1071 word sum of a 16-byte address given as frame-relative LE dwords: the four
 // host-order words' 16-bit halves (big-endian words, as the pseudo header sums them)
 __device__ __forceinline__ uint32_t addr_words_sum(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
@@ -793,31 +825,27 @@ __device__ __forceinline__ bool is_ip6_ext(uint32_t nh) {
 }
 
 // The IPv6 part of the parse (RPKT_F_IPV6, include/rpkt_gpu.h documents the record's
-// IPv6 block): Ipv6::parse (ipv6/generated.rs:40-51) and getters (:57-80, 194-205),
-// Ipv6::payload (:83-92: trim to 40 + payload_len, advance 40), then the extension
-// headers: each type's generated parse (DestOptions :241-252, HopByHopOption :384-395,
-// RoutingHeader :528-539, FragmentHeader :696-703, AuthenticationHeader :850-861) and
-// payload() = advance(header_len).  The 40-byte header always lies in the window (it
-// ends by frame byte 62); extension headers past it are read from global memory.
-// Returns the status; on OK: l4 (frame offset of the upper-layer header), its
-// remaining bytes, the protocol and the pseudo header's address sum.
-__device__ __forceinline__ uint32_t parse_ip6(const uint8_t* slot, uint32_t ph, Frame fr,
-                                              __amdgpu_buffer_rsrc_t rs, uint32_t fb,
-                                              uint32_t l3, uint32_t rem,
+// IPv6 block), over either view: Ipv6::parse (ipv6/generated.rs:40-51) and getters (:57-80,
+// 194-205), Ipv6::payload (:83-92: trim to 40 + payload_len, advance 40), then the
+// extension headers: each type's generated parse (DestOptions :241-252, HopByHopOption
+// :384-395, RoutingHeader :528-539, FragmentHeader :696-703, AuthenticationHeader :850-861)
+// and payload() = advance(header_len).  Every header size is tested against chunk() at the
+// header's first byte, the payload length against remaining() (over a Pbuf, as
+// oracle/rpkt_oracle_chain.c parse_pbuf_ip6).  l3: the header's cursor, pkt: the packet end.
+// A flat frame's 40-byte header always lies in the window (it ends by frame byte 62);
+// extension headers past it are read from global memory.
+// Returns the status; on OK: l4 (cursor of the upper-layer header), its remaining bytes,
+// the protocol and the pseudo header's address sum.
+template <class View>
+__device__ __forceinline__ uint32_t parse_ip6(const View& V, uint32_t l3, uint32_t pkt,
                                               uint32_t* w, uint32_t& l4, uint32_t& l4rem,
                                               uint32_t& proto, uint32_t& paddr) {
-    if (rem < 40u) return RPKT_S_IP6_SHORT;                               // :42
+    uint32_t at;
+    if (V.chunk(l3, pkt, at) < 40u) return RPKT_S_IP6_SHORT;              // :42
     uint32_t F[10];
-    {
-        const uint32_t x = ph + l3, a0 = x & ~3u, sh = x & 3u;
-        uint32_t R[11];
-#pragma unroll
-        for (int k = 0; k < 11; ++k) R[k] = lds32(slot, a0 + 4 * k);
-#pragma unroll
-        for (int k = 0; k < 10; ++k) F[k] = align_bytes(R[k + 1], R[k], sh);
-    }
+    V.template read_words<10>(at, F);
     const uint32_t plen = be16_lo(F[1]);                                  // payload_len :77-79
-    if (plen + 40u > rem) return RPKT_S_IP6_BAD_LEN;                      // :47
+    if (plen + 40u > pkt - l3) return RPKT_S_IP6_BAD_LEN;                 // :47
     w[6] = bswap32(F[0]);                                                 // version, tc, flow
     w[7] = plen | (F[1] & 0xffff0000u);                                   // next_header, hop_limit
     w[9] = bswap32(F[2]) ^ bswap32(F[3]) ^ bswap32(F[4]) ^ bswap32(F[5]);    // src fold
@@ -825,16 +853,15 @@ __device__ __forceinline__ uint32_t parse_ip6(const uint8_t* slot, uint32_t ph, 
     const uint32_t src_sum = addr_words_sum(F[2], F[3], F[4], F[5]);
     uint32_t pdst_sum = addr_words_sum(F[6], F[7], F[8], F[9]);
     uint32_t pdst_off = l3 + 24u;
-    const FrameDw dw{slot, ph, fr.off, fb, rs};
     uint32_t c = l3 + 40u;
-    const uint32_t end = c + plen;
+    const uint32_t end = c + plen;                                        // payload() trim
     uint32_t nh = (F[1] >> 16) & 0xffu, n_ext = 0, status = RPKT_S_OK;
     for (int k = 0; k < RPKT_MAX_IP6_EXT && is_ip6_ext(nh); ++k) {
         const bool fg = nh == 44u, ah = nh == 51u, rt = nh == 43u;
         const uint32_t fixed = (nh == 0u || nh == 60u) ? 2u : (ah ? 12u : 8u);
-        const uint32_t cl = end - c;                                      // chunk_len
+        const uint32_t cl = V.chunk(c, end, at);                          // chunk_len
         if (cl < fixed) { status = RPKT_S_IP6_EXT_SHORT; break; }
-        const uint32_t d0 = dw(c);                 // next_header, len, (type, segments_left)
+        const uint32_t d0 = V.dw(at);              // next_header, len, (type, segments_left)
         const uint32_t b1 = (d0 >> 8) & 0xffu;
         const uint32_t hl = fg ? 8u : (ah ? b1 * 4u + 8u : b1 * 8u + 8u);    // header_len
         if (!fg && (hl < fixed || hl > cl)) { status = RPKT_S_IP6_EXT_BAD_LEN; break; }
@@ -843,9 +870,10 @@ __device__ __forceinline__ uint32_t parse_ip6(const uint8_t* slot, uint32_t ph, 
             // (RFC 8200 section 8.1): the last of the list (types 0, 2), Segment List[0] (4)
             const uint32_t type = (d0 >> 16) & 0xffu, n_addr = (hl - 8u) >> 4;
             if (n_addr != 0u && (type == 0u || type == 2u || type == 4u)) {
-                const uint32_t a = c + 8u + (type == 4u ? 0u : 16u * (n_addr - 1u));
-                pdst_off = a;
-                pdst_sum = addr_words_sum(dw(a), dw(a + 4u), dw(a + 8u), dw(a + 12u));
+                const uint32_t r = 8u + (type == 4u ? 0u : 16u * (n_addr - 1u));
+                pdst_off = c + r;
+                pdst_sum = addr_words_sum(V.dw(at + r), V.dw(at + r + 4u), V.dw(at + r + 8u),
+                                          V.dw(at + r + 12u));
             }
         }
         nh = d0 & 0xffu;
@@ -861,6 +889,88 @@ __device__ __forceinline__ uint32_t parse_ip6(const uint8_t* slot, uint32_t ph, 
     proto = nh;
     paddr = src_sum + pdst_sum;
     return status;
+}
+
+// Ipv4::parse (ipv4/generated.rs:35-51) and getters (:61-112, 269-288) on the header's
+// first 20 bytes F (frame-relative LE dwords; anything when ck < 20): the header sizes
+// against ck = chunk().len() at the header, the total length against rem = remaining().
+// Returns the status; on OK record words 6..10 are written and o holds the header length,
+// the total length, the protocol and the pseudo header's address sum (smoltcp
+// pseudo_header_v4: src, dst).  No memory access: each lane parser fetches F its own way.
+struct Ip4Out { uint32_t status, ihl4, tot, proto, paddr; };
+__device__ __forceinline__ Ip4Out ip4_rules(const uint32_t (&F)[5], uint32_t ck, uint32_t rem,
+                                            uint32_t* w) {
+    Ip4Out o{RPKT_S_OK, (F[0] & 0xfu) * 4u, be16_hi(F[0]), 0u, 0u};
+    if (ck < 20) o.status = RPKT_S_IP_SHORT;
+    else if (o.ihl4 < 20) o.status = RPKT_S_IP_BAD_IHL;
+    else if (o.ihl4 > ck) o.status = RPKT_S_IP_IHL_GT_LEN;
+    else if (o.tot < o.ihl4) o.status = RPKT_S_IP_TOT_LT_IHL;
+    else if (o.tot > rem) o.status = RPKT_S_IP_TOT_GT_LEN;
+    const uint32_t src = bswap32(F[3]), dst = bswap32(F[4]);
+    o.proto = (F[2] >> 8) & 0xffu;
+    o.paddr = (src >> 16) + (src & 0xffffu) + (dst >> 16) + (dst & 0xffffu);
+    if (o.status == RPKT_S_OK) {
+        w[6] = (F[0] & 0xffffu) | (o.tot << 16);
+        w[7] = be16_lo(F[1]) | (be16_hi(F[1]) << 16);
+        w[8] = (F[2] & 0xffffu) | (be16_hi(F[2]) << 16);
+        w[9] = src;
+        w[10] = dst;
+    }
+    return o;
+}
+
+// Udp::parse (udp/generated.rs:31-42) / Tcp::parse (tcp/generated.rs:34-45) and their
+// getters on the L4 header's first 20 bytes H, or the protocols with a sum of another kind:
+// header sizes against ck = chunk().len() at l4, lengths against l4rem = remaining() under
+// the IP layer's trim.  pos: l4 as the record holds it.  Returns the status; writes record
+// words 11..15 and, for UDP / TCP, word 17 (the payload's offset and length); l4len: the
+// bytes the L4 sum covers; other_sum: that sum has no pseudo header.  No memory access.
+struct L4Out { uint32_t status, l4len; bool other_sum; };
+__device__ __forceinline__ L4Out l4_rules(const uint32_t (&H)[5], uint32_t ck, uint32_t l4rem,
+                                             uint32_t proto, bool v6, uint32_t pos, uint32_t* w) {
+    uint32_t status = RPKT_S_OK;
+    uint32_t l4len = 0;
+    bool other_sum = false;
+    if (proto == 17u) {
+        const uint32_t ulen = be16_lo(H[1]);
+        if (ck < 8) status = RPKT_S_UDP_SHORT;
+        else if (ulen < 8 || ulen > l4rem) status = RPKT_S_UDP_BAD_LEN;
+        else {
+            w[11] = be16_lo(H[0]) | (be16_hi(H[0]) << 16);
+            w[14] = ulen;
+            w[15] = be16_hi(H[1]);
+            w[17] = ((pos + 8) & 0xffffu) | ((ulen - 8) << 16);          // Udp::payload :66-76
+            l4len = ulen;
+        }
+    } else if (proto == 6u) {
+        const uint32_t hl = ((H[3] >> 4) & 0xfu) * 4u;
+        if (ck < 20) status = RPKT_S_TCP_SHORT;
+        else if (hl < 20 || hl > ck) status = RPKT_S_TCP_BAD_DOFF;
+        else {
+            w[11] = be16_lo(H[0]) | (be16_hi(H[0]) << 16);
+            w[12] = bswap32(H[1]);
+            w[13] = bswap32(H[2]);
+            w[14] = be16_lo(H[3]) | (be16_hi(H[3]) << 16);
+            w[15] = be16_lo(H[4]) | (be16_hi(H[4]) << 16);
+            w[17] = ((pos + hl) & 0xffffu) | ((l4rem - hl) << 16);       // Tcp::payload :125-131
+            l4len = l4rem;
+        }
+    } else {
+        status = RPKT_S_L4_OTHER;
+        // ICMP (IPv4 protocol 1; calculate_icmp_checksum, icmpv4/generated.rs:2678-2701, is
+        // the complement of this sum; an empty payload panics there: ICMP_EMPTY) and GRE
+        // with checksum_present (gre/generated.rs:55; RFC 2784 section 2.5; the GRE header's
+        // first byte is the first byte of the chunk at l4): the sum over the whole IP
+        // payload, no pseudo header (include/rpkt_gpu.h, l4_sum)
+        if (!v6 && proto == 1u) {
+            if (l4rem == 0u) status = RPKT_S_ICMP_EMPTY;
+            else other_sum = true;
+        } else if (proto == 47u && l4rem >= 4u && (H[0] & 0x80u)) {
+            other_sum = true;
+        }
+        l4len = l4rem;
+    }
+    return L4Out{status, l4len, other_sum};
 }
 
 // Lane-per-frame parse from the LDS window: the rpkt chain with every getter, the
@@ -948,7 +1058,7 @@ __device__ __forceinline__ void parse_lane(const WaveScratch& W, int lane, Frame
     if (v6) {
         // round 2 (IPv6): the header, the extension headers, the pseudo header's addresses
         L.is6 = true;
-        status = parse_ip6(slot, ph, fr, rs, fb, l3, rem, w, l4, l4rem, proto, paddr);
+        status = parse_ip6(FlatView{{slot, ph, fr.off, fb, rs}}, l3, len, w, l4, l4rem, proto, paddr);
         if (status != RPKT_S_IP6_SHORT && status != RPKT_S_IP6_BAD_LEN) {
             w[16] |= (base + l4) << 16;
             w[17] = ((base + l4) & 0xffffu) | (l4rem << 16);
@@ -960,40 +1070,27 @@ __device__ __forceinline__ void parse_lane(const WaveScratch& W, int lane, Frame
             return;
         }
     } else {
-        // round 2: Ipv4::parse (ipv4/generated.rs:35-51) and getters (:61-112, 269-288)
+        // round 2: Ipv4::parse and getters; over a flat frame chunk() is remaining()
         Hdr6 ip;
         read_hdr(slot, ph + l3, ip);
-        const uint32_t vhl = ip.F[0] & 0xffu;
-        const uint32_t ihl4 = (vhl & 0xfu) * 4u;
-        const uint32_t tot = be16_hi(ip.F[0]);
-        if (rem < 20) status = RPKT_S_IP_SHORT;
-        else if (ihl4 < 20) status = RPKT_S_IP_BAD_IHL;
-        else if (ihl4 > rem) status = RPKT_S_IP_IHL_GT_LEN;
-        else if (tot < ihl4) status = RPKT_S_IP_TOT_LT_IHL;
-        else if (tot > rem) status = RPKT_S_IP_TOT_GT_LEN;
+        const Ip4Out o = ip4_rules(ip.F, rem, rem, w);
+        status = o.status;
         if (status != RPKT_S_OK) {
             w[0] |= status;
             L.status = status;
             return;
         }
-        proto = (ip.F[2] >> 8) & 0xffu;
-        const uint32_t src = bswap32(ip.F[3]), dst = bswap32(ip.F[4]);
-        w[6] = (ip.F[0] & 0xffffu) | (tot << 16);
-        w[7] = be16_lo(ip.F[1]) | (be16_hi(ip.F[1]) << 16);
-        w[8] = (ip.F[2] & 0xffffu) | (be16_hi(ip.F[2]) << 16);
-        w[9] = src;
-        w[10] = dst;
         if (flags & RPKT_F_IP_SUM)
-            w[18] = be_sum(raw_range_sum(slot, ip.R, ip.a0, ph + l3, ph + l3 + ihl4), fr.off + l3);
-        l4 = l3 + ihl4;                                        // Ipv4::payload :115-127
-        l4rem = tot - ihl4;
+            w[18] = be_sum(raw_range_sum(slot, ip.R, ip.a0, ph + l3, ph + l3 + o.ihl4), fr.off + l3);
+        l4 = l3 + o.ihl4;                                      // Ipv4::payload :115-127
+        l4rem = o.tot - o.ihl4;
         w[16] |= (base + l4) << 16;
         w[17] = (base + l4) | (l4rem << 16);
-        // pseudo header (smoltcp pseudo_header_v4): src, dst
-        paddr = (src >> 16) + (src & 0xffffu) + (dst >> 16) + (dst & 0xffffu);
+        proto = o.proto;
+        paddr = o.paddr;
     }
 
-    // round 3: Udp::parse (udp/generated.rs:31-42) / Tcp::parse (tcp/generated.rs:34-45).
+    // round 3: Udp::parse / Tcp::parse (l4_rules).
     // An IPv4 L4 header always lies in the window (l4 <= 82); an IPv6 one past its
     // extension headers may not: its fields are then read from global memory, and the
     // in-window part of its sum is whatever of it the window holds.
@@ -1003,46 +1100,10 @@ __device__ __forceinline__ void parse_lane(const WaveScratch& W, int lane, Frame
     // an untagged IPv6/UDP frame's header, bytes 54..61, in LDS)
     if (v6 && __builtin_expect(ph + l4 + (proto == 17u ? 8u : 20u) > (uint32_t)kWin, 0))
         gread20(rs, fb, fr.off + l4, h4.F);
-    uint32_t l4len = 0;
-    bool other_sum = false;                                    // ICMP / GRE: no pseudo header
-    if (proto == 17u) {
-        const uint32_t ulen = be16_lo(h4.F[1]);
-        if (l4rem < 8) status = RPKT_S_UDP_SHORT;
-        else if (ulen < 8 || ulen > l4rem) status = RPKT_S_UDP_BAD_LEN;
-        else {
-            w[11] = be16_lo(h4.F[0]) | (be16_hi(h4.F[0]) << 16);
-            w[14] = ulen;
-            w[15] = be16_hi(h4.F[1]);
-            w[17] = ((base + l4 + 8) & 0xffffu) | ((ulen - 8) << 16);   // Udp::payload :66-76
-            l4len = ulen;
-        }
-    } else if (proto == 6u) {
-        const uint32_t hl = ((h4.F[3] >> 4) & 0xfu) * 4u;
-        if (l4rem < 20) status = RPKT_S_TCP_SHORT;
-        else if (hl < 20 || hl > l4rem) status = RPKT_S_TCP_BAD_DOFF;
-        else {
-            w[11] = be16_lo(h4.F[0]) | (be16_hi(h4.F[0]) << 16);
-            w[12] = bswap32(h4.F[1]);
-            w[13] = bswap32(h4.F[2]);
-            w[14] = be16_lo(h4.F[3]) | (be16_hi(h4.F[3]) << 16);
-            w[15] = be16_lo(h4.F[4]) | (be16_hi(h4.F[4]) << 16);
-            w[17] = ((base + l4 + hl) & 0xffffu) | ((l4rem - hl) << 16);   // Tcp::payload :125-131
-            l4len = l4rem;
-        }
-    } else {
-        status = RPKT_S_L4_OTHER;
-        // ICMP (IPv4 protocol 1; calculate_icmp_checksum, icmpv4/generated.rs:2678-2701, is
-        // the complement of this sum; an empty payload panics there: ICMP_EMPTY) and GRE
-        // with checksum_present (gre/generated.rs:55; RFC 2784 section 2.5): the sum over
-        // the whole IP payload, no pseudo header (include/rpkt_gpu.h, l4_sum)
-        if (!v6 && proto == 1u) {
-            if (l4rem == 0u) status = RPKT_S_ICMP_EMPTY;
-            else other_sum = true;
-        } else if (proto == 47u && l4rem >= 4u && (h4.F[0] & 0x80u)) {
-            other_sum = true;
-        }
-        l4len = l4rem;
-    }
+    const L4Out r4 = l4_rules(h4.F, l4rem, l4rem, proto, v6, base + l4, w);
+    status = r4.status;
+    const uint32_t l4len = r4.l4len;
+    const bool other_sum = r4.other_sum;
     w[0] |= status;
     L.status = status;
     if ((status == RPKT_S_OK || other_sum) && (flags & RPKT_F_L4_SUM)) {

@@ -6,7 +6,7 @@
 // One wavefront per tile, as parse_kernel: the outer header windows go to LDS (on long
 // tiles together with each frame's tail line, whose sum is taken there and then) and each
 // lane runs parse_lane on its frame; the lane then decodes the tunnel header(s) from the
-// same window (FrameDw: global memory past it).  The outer record waits in registers (its
+// same window (FlatView: global memory past it).  The outer record waits in registers (its
 // words 0..11 in LDS past the inner record's stage once that is written: 128 VGPRs and
 // 9.7 KB of LDS per wave, 16 waves per CU), and the inner frame's window is made from the
 // outer one: the chunks they share move down the lane's slot and only the chunks past the
@@ -167,7 +167,7 @@ __device__ __forceinline__ void tunnel_tile(WaveScratch& W,
     parse_lane(W, lane, fr, valid, flags, L, rs, fb);
 
     // 2. the tunnel, from the outer window
-    const Tunnel T = decode_tunnel(L, FrameDw{&W.win[lane * kSlot], fr.off & 15u, fr.off, fb, rs},
+    const Tunnel T = decode_tunnel(L, FlatView{{&W.win[lane * kSlot], fr.off & 15u, fr.off, fb, rs}},
                                    flags);
 
     // 3. the outer record in registers through the inner parse (a second LDS stage for it
@@ -188,13 +188,7 @@ __device__ __forceinline__ void tunnel_tile(WaveScratch& W,
     // is summed from it below, and it can run past the inner frame)
     inner_window_reuse(rs, fb, W, lane, a1, T.ok ? keep : (uint32_t)kWinChunks, fend);
     parse_lane(W, lane, fi, T.ok, flags, L, rs, fb, T.start_et, T.is);
-    if (!T.ok) {
-#pragma unroll
-        for (int k = 0; k < 20; ++k) L.w[k] = 0u;
-        L.w[0] = RPKT_S_NO_INNER;
-        L.want_l4 = false;
-        L.stream_s = L.stream_e = 0u;
-    }
+    if (!T.ok) no_inner(L);
     // the outer L4 range's bytes the inner window holds: [max(o_ss, a1), min(o_se, a1 + 128))
     [[maybe_unused]] uint32_t o_lds = 0u;
     if constexpr (L4) {
@@ -249,8 +243,7 @@ __device__ __forceinline__ void tunnel_tile(WaveScratch& W,
     if (ev && !T.ok) __builtin_nontemporal_store(record_event(ow, n_buckets), &flow_ev[i]);
     stage_record(W, lane, ow);
     flush_stage(rec_stage(W), lane, outer, p0, n);
-    if (valid) __builtin_nontemporal_store(u32x4{T.w[0], T.w[1], T.w[2], T.w[3]},
-                                           reinterpret_cast<u32x4*>(tun) + i);
+    if (valid) store_tun(tun, i, T);
 }
 
 // One wave per workgroup (as the parse: a CU slot frees when its wave ends); 9.7 KB of LDS

@@ -6,9 +6,9 @@
 // One wavefront per 64 chains, as parse_chains_kernel: segment 0's 128-B window goes to LDS
 // and each lane runs parse_chain_lane on its chain.  The lane then decodes the tunnel and
 // parses the inner frame with logical cursors in the chain's bytes: every header-size test
-// takes chunk() at the header's cursor under the current packet end (ChainView::chunk: the
-// rest of segment 0 below its end, chain_chunk's segment walk past it), every total-length
-// test takes remaining(), and header bytes come through ChainDw (LDS when they lie in
+// takes chunk() at the header's cursor under the current packet end (ChainView, rpkt_chain.h:
+// the rest of segment 0 below its end, chain_chunk's segment walk past it), every
+// total-length test takes remaining(), and header bytes come through ChainDw (LDS when they lie in
 // segment 0's window, byte-wise global loads otherwise -- a header that starts past the
 // window or in a later segment; there is no second inner window).  The outer record is
 // staged in an LDS area of its own, the inner one in the window area, so chain_stream keeps
@@ -23,151 +23,6 @@
 
 namespace {
 
-// The lane's chain as a Pbuf: chunk() at logical cursor c under the packet end lim (the
-// trim of the views above it).  Below segment 0's end C the chunk is the rest of segment
-// 0; past it chain_chunk walks the segments (empty ones skipped, as advance_common).
-// abs = the chunk's first byte (fb, where every load returns 0, when the chunk is empty).
-struct ChainView {
-    ChainSrc S;
-    uint32_t a, b, off0, C;
-    __device__ __forceinline__ uint32_t chunk(uint32_t c, uint32_t lim, uint32_t& abs) const {
-        abs = S.fb;
-        if (c >= lim) return 0u;
-        if (c < C) {
-            abs = off0 + c;
-            return (C < lim ? C : lim) - c;
-        }
-        return chain_chunk(S, a, b, c, lim, abs);
-    }
-};
-
-// decode_tunnel (rpkt_tunnel.h) over a Pbuf: the same dispatch and the same getters, with
-// each parse's header-size tests against chunk() at its cursor and its total-length tests
-// against remaining() (the views' own split: a header that straddles a segment boundary is
-// Err there, T_BAD / T_EXT_BAD here).  ts, te, T.is, T.ie are logical positions in the chain.
-__device__ __forceinline__ Tunnel decode_tunnel_chain(const LaneRec& L, const ChainDw& dw,
-                                                      const ChainView& V, uint32_t flags) {
-    Tunnel T;
-    T.w[0] = RPKT_TUN_NONE | (RPKT_T_NONE << 8);
-    T.w[1] = T.w[2] = T.w[3] = 0u;
-    T.is = T.ie = T.start_et = 0u;
-    T.ok = false;
-    const uint32_t* w = L.w;
-    const uint32_t proto = (w[8] >> 8) & 0xffu;              // ip_protocol (IPv4 and IPv6)
-    uint32_t kind = RPKT_TUN_NONE, ts = 0u, te = 0u;
-    if (L.status == RPKT_S_OK && proto == 17u) {
-        // Udp::payload() (udp/generated.rs:66-76): [payload_off, + payload_len)
-        const uint32_t dp = w[11] >> 16, sp = w[11] & 0xffffu;
-        const uint32_t port = (dp == 4789u || dp == 2152u) ? dp
-                            : ((sp == 4789u || sp == 2152u) ? sp : 0u);
-        if (port != 0u) {
-            kind = port == 4789u ? RPKT_TUN_VXLAN : RPKT_TUN_GTPU;
-            ts = w[17] & 0xffffu;
-            te = ts + (w[17] >> 16);
-        }
-    } else if (L.status == RPKT_S_L4_OTHER && proto == 47u &&
-               (L.is6 || ((w[7] >> 16) & 0x1fffu) == 0u)) {
-        // Ipv4|Ipv6::payload() of a first (or only) fragment: [l4_off, + payload_len)
-        kind = RPKT_TUN_GRE;
-        ts = w[16] >> 16;
-        te = ts + (w[17] >> 16);
-    }
-    if (kind == RPKT_TUN_NONE) return T;
-    uint32_t ab;
-    const uint32_t cl = V.chunk(ts, te, ab), rm = te - ts;   // chunk().len(), remaining()
-    tun_set(T, kind, RPKT_T_BAD, ts, 0u, 0u);
-    if (kind == RPKT_TUN_VXLAN) {
-        // Vxlan::parse (vxlan/generated.rs:32-39): chunk_len >= 8
-        if (cl < 8u) return T;
-        const uint32_t d0 = dw(ab), d1 = dw(ab + 4u);
-        T.w[2] = bswap32(d1) >> 8;                            // vni, bytes 4..6
-        T.w[3] = (d0 & 0xffffu) | (be16_hi(d0) << 16);        // flags bytes 0, 1; group_id
-        tun_inner(T, kind, ts, ts + 8u, te, 0x6558u, flags);
-        return T;
-    }
-    if (kind == RPKT_TUN_GTPU) {
-        // Gtpv1::parse (gtpv1/generated.rs:33-49): chunk_len >= 8, header_len <= chunk_len,
-        // header_len <= packet_len <= remaining
-        if (cl < 8u) return T;
-        const uint32_t d0 = dw(ab);
-        const uint32_t b0 = d0 & 0xffu, msg = (d0 >> 8) & 0xffu;
-        const uint32_t hl = (b0 & 7u) ? 12u : 8u;
-        const uint32_t plen = be16_hi(d0) + 8u;
-        if (hl > cl || plen < hl || plen > rm) return T;
-        const uint32_t d2 = hl == 12u ? dw(ab + 8u) : 0u;
-        T.w[2] = bswap32(dw(ab + 4u));                        // teid :74-76
-        T.w[3] = (d0 & 0xffffu) | (be16_lo(d2) << 16);        // byte 0, message_type; sequence
-        // payload() :98-108: trim to packet_len, advance header_len
-        uint32_t c = ts + hl;
-        const uint32_t end = ts + plen;
-        if ((b0 >> 5) != 1u || msg != 255u) {                 // not a GTPv1 G-PDU
-            tun_set(T, kind, RPKT_T_NOT_TPDU, ts, c, 0u);
-            return T;
-        }
-        // the extension headers, each parsed against its own chunk (:336-341, :461-466,
-        // :587-592, :747-752, :880-892 and the NrUp / PduSessionUp group parses)
-        uint32_t nx = (b0 & 4u) ? (d2 >> 24) : 0u;
-        for (int k = 0; k < RPKT_MAX_GTP_EXT && nx != 0u; ++k) {
-            uint32_t ax;
-            const uint32_t rem = V.chunk(c, end, ax), x = dw(ax);
-            const uint32_t e0 = x & 0xffu, t = (x >> 12) & 0xfu;
-            uint32_t need, mn, ehl;
-            if (nx == 0x40u || nx == 0xc0u || nx == 0x20u) {
-                need = 4u; mn = 4u; ehl = 4u;
-            } else if (nx == 0x03u || nx == 0x82u) {
-                need = 8u; mn = 8u; ehl = 8u;
-            } else if (nx == 0x81u || nx == 0x83u) {
-                need = 1u; mn = 1u; ehl = e0 * 4u;
-            } else if (nx == 0x84u && t <= 2u) {
-                need = 2u; mn = t == 0u ? 6u : (t == 1u ? 7u : 3u); ehl = e0 * 4u;
-            } else if (nx == 0x85u && t <= 1u) {
-                need = 2u; mn = 3u; ehl = e0 * 4u;
-            } else {
-                need = ~0u; mn = 0u; ehl = 0u;                // unknown type / group Err
-            }
-            if (rem < need || rem < mn || ehl < mn || ehl > rem) {
-                tun_set(T, kind, RPKT_T_EXT_BAD, ts, c, 0u);
-                return T;
-            }
-            nx = dw(ax + ehl - 1u) & 0xffu;                   // next_extention_header: last byte
-            c += ehl;
-        }
-        if (nx != 0u) {
-            tun_set(T, kind, RPKT_T_EXT_BAD, ts, c, 0u);
-            return T;
-        }
-        // the T-PDU: Ipv4 / Ipv6 by the version nibble of the cursor's first byte
-        uint32_t ax;
-        const uint32_t v = V.chunk(c, end, ax) ? (dw(ax) >> 4) & 0xfu : 0u;
-        tun_inner(T, kind, ts, c, end, v == 4u ? 0x0800u : (v == 6u ? 0x86ddu : 0u), flags);
-        return T;
-    }
-    // GreGroup::group_parse (gre/generated.rs:800-820): chunk >= 4; GreForPPTP::parse
-    // (:371-386): chunk >= 8, header_len <= chunk, payload_len + header_len <= remaining;
-    // Gre::parse (:33-44): header_len in [4, chunk]
-    if (cl < 4u) return T;
-    const uint32_t d0 = dw(ab);
-    const uint32_t b0 = d0 & 0xffu, b1 = (d0 >> 8) & 0xffu, pt = be16_hi(d0), ver = b1 & 7u;
-    if ((b0 & 0xe0u) == 0x20u && ver == 1u && pt == 0x880bu) {
-        if (cl < 8u) return T;
-        const uint32_t d1 = dw(ab + 4u);
-        const uint32_t phl = 8u + ((b0 & 0x10u) ? 4u : 0u) + ((b1 & 0x80u) ? 4u : 0u);
-        if (phl > cl || be16_lo(d1) + phl > rm) return T;
-        T.w[2] = bswap32(d1);                                 // payload_len, call_id
-        T.w[3] = d0 & 0xffffu;
-        tun_set(T, kind, RPKT_T_INNER_UNKNOWN, ts, ts + phl, pt);   // PPP, not IP
-        return T;
-    }
-    if (ver != 0u) return T;
-    const uint32_t cr = (b0 & 0xc0u) ? 4u : 0u;
-    const uint32_t hl = 4u + cr + ((b0 & 0x20u) ? 4u : 0u) + ((b0 & 0x10u) ? 4u : 0u);
-    if (hl > cl) return T;
-    T.w[3] = (d0 & 0xffffu) | (cr ? be16_lo(dw(ab + 4u)) << 16 : 0u);   // checksum :236-241
-    if (b0 & 0x20u) T.w[2] = bswap32(dw(ab + 4u + cr));        // key :260-267
-    tun_inner(T, kind, ts, ts + hl, te, pt, flags);           // payload() advance header_len
-    return T;
-}
-
 // Big-endian sum of the n <= chunk bytes of a header at absolute `ab`: from segment 0's
 // window when they lie in it, else byte-wise (gsum_be).
 __device__ __forceinline__ uint32_t header_sum(const ChainDw& dw, uint32_t ab, uint32_t n) {
@@ -181,10 +36,12 @@ __device__ __forceinline__ uint32_t header_sum(const ChainDw& dw, uint32_t ab, u
 // started at its Ethernet header (T.start_et 0) or at its IP header (GTP-U, GRE over IP:
 // MACs 0, no tags, ethertype = the tunnel's dispatch value).  Cursors and the record's
 // offsets are logical positions in the outer chain; frame_len is the sub-chain's length.
-// The same tests as parse_chain_lane, each chunk taken by V.chunk at the header's cursor
-// under the current end, each header read through dw.
-__device__ __forceinline__ void parse_inner_lane(const ChainDw& dw, const ChainView& V,
-                                                 const Tunnel& T, uint32_t flags, LaneRec& L) {
+// The rules are the shared ones (parse_ip6, ip4_rules, l4_rules); what is here is the link
+// layer and the cursors, every header read through the view: parse_chain_lane's own rounds
+// are built on segment 0's window at cursor 0 (bulk LDS reads, raw_range_sum on them), and
+// an inner frame starts anywhere in the chain.
+__device__ __forceinline__ void parse_inner_lane(const ChainView& V, const Tunnel& T,
+                                                 uint32_t flags, LaneRec& L) {
     uint32_t* w = L.w;
 #pragma unroll
     for (int k = 0; k < 20; ++k) w[k] = 0;
@@ -200,10 +57,10 @@ __device__ __forceinline__ void parse_inner_lane(const ChainDw& dw, const ChainV
             w[0] = RPKT_S_ETH_SHORT;
             return;
         }
-        w[1] = dw(ab);
-        w[2] = dw(ab + 4u);
-        w[3] = dw(ab + 8u);
-        const uint32_t eth_et = be16_lo(dw(ab + 12u));
+        w[1] = V.dw(ab);
+        w[2] = V.dw(ab + 4u);
+        w[3] = V.dw(ab + 8u);
+        const uint32_t eth_et = be16_lo(V.dw(ab + 12u));
         uint32_t nvlan = 0;
         et = eth_et;
         c += 14u;
@@ -213,7 +70,7 @@ __device__ __forceinline__ void parse_inner_lane(const ChainDw& dw, const ChainV
                 status = RPKT_S_VLAN_SHORT;
                 break;
             }
-            const uint32_t t = dw(ab);
+            const uint32_t t = V.dw(ab);
             et = be16_hi(t);
             w[4] |= be16_lo(t) << (16 * v);
             w[5] |= et << (16 * v);
@@ -237,7 +94,7 @@ __device__ __forceinline__ void parse_inner_lane(const ChainDw& dw, const ChainV
     uint32_t l4, limit, l4rem, proto, paddr;
     if (v6) {
         L.is6 = true;
-        status = parse_chain_ip6(dw, V.C, pkt, V.S, V.a, V.b, l3, w, l4, l4rem, proto, paddr);
+        status = parse_ip6(V, l3, pkt, w, l4, l4rem, proto, paddr);
         if (status != RPKT_S_IP6_SHORT && status != RPKT_S_IP6_BAD_LEN) {
             w[16] |= l4 << 16;
             w[17] = (l4 & 0xffffu) | (l4rem << 16);
@@ -249,84 +106,38 @@ __device__ __forceinline__ void parse_inner_lane(const ChainDw& dw, const ChainV
         }
         limit = l4 + l4rem;
     } else {
-        // Ipv4::parse (ipv4/generated.rs:35-51): chunk vs remaining
         const uint32_t ck3 = V.chunk(l3, pkt, ab);
-        uint32_t F[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) F[k] = ck3 >= 20u ? dw(ab + 4u * k) : 0u;
-        const uint32_t ihl4 = (F[0] & 0xfu) * 4u;
-        const uint32_t tot = be16_hi(F[0]);
-        if (ck3 < 20) status = RPKT_S_IP_SHORT;
-        else if (ihl4 < 20) status = RPKT_S_IP_BAD_IHL;
-        else if (ihl4 > ck3) status = RPKT_S_IP_IHL_GT_LEN;
-        else if (tot < ihl4) status = RPKT_S_IP_TOT_LT_IHL;
-        else if (tot > pkt - l3) status = RPKT_S_IP_TOT_GT_LEN;
+        uint32_t F[5] = {0u, 0u, 0u, 0u, 0u};
+        if (ck3 >= 20u) V.read_words(ab, F);
+        const Ip4Out o = ip4_rules(F, ck3, pkt - l3, w);
+        status = o.status;
         if (status != RPKT_S_OK) {
             w[0] |= status;
             L.status = status;
             return;
         }
-        proto = (F[2] >> 8) & 0xffu;
-        const uint32_t src = bswap32(F[3]), dst = bswap32(F[4]);
-        w[6] = (F[0] & 0xffffu) | (tot << 16);
-        w[7] = be16_lo(F[1]) | (be16_hi(F[1]) << 16);
-        w[8] = (F[2] & 0xffffu) | (be16_hi(F[2]) << 16);
-        w[9] = src;
-        w[10] = dst;
-        if (flags & RPKT_F_IP_SUM) w[18] = header_sum(dw, ab, ihl4);
-        l4 = l3 + ihl4;                                        // Ipv4::payload :115-127
-        limit = l3 + tot;
-        l4rem = tot - ihl4;
+        if (flags & RPKT_F_IP_SUM) w[18] = header_sum(V.d, ab, o.ihl4);
+        l4 = l3 + o.ihl4;                                      // Ipv4::payload :115-127
+        limit = l3 + o.tot;
+        l4rem = o.tot - o.ihl4;
         w[16] |= l4 << 16;
         w[17] = (l4 & 0xffffu) | (l4rem << 16);
-        paddr = (src >> 16) + (src & 0xffffu) + (dst >> 16) + (dst & 0xffffu);
+        proto = o.proto;
+        paddr = o.paddr;
     }
 
-    // Udp::parse / Tcp::parse against the chunk at l4 under the trimmed end
-    uint32_t ab4;
+    // the L4 header against the chunk at l4 under the trimmed end
+    uint32_t ab4, H[5];
     const uint32_t ck4 = V.chunk(l4, limit, ab4);
-    uint32_t H[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) H[k] = dw(ab4 + 4u * k);
-    uint32_t l4len = 0;
-    bool other_sum = false;                                    // ICMP / GRE (parse_lane)
-    if (proto == 17u) {
-        const uint32_t ulen = be16_lo(H[1]);
-        if (ck4 < 8) status = RPKT_S_UDP_SHORT;
-        else if (ulen < 8 || ulen > l4rem) status = RPKT_S_UDP_BAD_LEN;
-        else {
-            w[11] = be16_lo(H[0]) | (be16_hi(H[0]) << 16);
-            w[14] = ulen;
-            w[15] = be16_hi(H[1]);
-            w[17] = ((l4 + 8) & 0xffffu) | ((ulen - 8) << 16);
-            l4len = ulen;
-        }
-    } else if (proto == 6u) {
-        const uint32_t hl = ((H[3] >> 4) & 0xfu) * 4u;
-        if (ck4 < 20) status = RPKT_S_TCP_SHORT;
-        else if (hl < 20 || hl > ck4) status = RPKT_S_TCP_BAD_DOFF;
-        else {
-            w[11] = be16_lo(H[0]) | (be16_hi(H[0]) << 16);
-            w[12] = bswap32(H[1]);
-            w[13] = bswap32(H[2]);
-            w[14] = be16_lo(H[3]) | (be16_hi(H[3]) << 16);
-            w[15] = be16_lo(H[4]) | (be16_hi(H[4]) << 16);
-            w[17] = ((l4 + hl) & 0xffffu) | ((l4rem - hl) << 16);
-            l4len = l4rem;
-        }
-    } else {
-        status = RPKT_S_L4_OTHER;
-        if (!v6 && proto == 1u) {
-            if (l4rem == 0u) status = RPKT_S_ICMP_EMPTY;
-            else other_sum = true;
-        } else if (proto == 47u && l4rem >= 4u && (H[0] & 0x80u)) {
-            other_sum = true;
-        }
-        l4len = l4rem;
-    }
+    V.read_words(ab4, H);
+    const L4Out r4 = l4_rules(H, ck4, l4rem, proto, v6, l4, w);
+    status = r4.status;
+    const uint32_t l4len = r4.l4len;
+    const bool other_sum = r4.other_sum;                       // ICMP / GRE
     w[0] |= status;
     L.status = status;
     if ((status == RPKT_S_OK || other_sum) && (flags & RPKT_F_L4_SUM)) {
+        const ChainDw& dw = V.d;
         L.want_l4 = true;
         L.pseudo = other_sum ? 0u : paddr + proto + l4len;
         const uint32_t e = l4 + l4len;
@@ -400,19 +211,10 @@ void tunnel_chains_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
     [[maybe_unused]] const bool o_want = L.want_l4;
 
     // 2. the tunnel and the inner frame, from the same window (byte-wise past it)
-    const uint32_t ph = s0.off & 15u, wl = (uint32_t)kWin - ph;
-    const ChainDw dw{&W.win[lane * kSlot], ph, s0.off, s0.len < wl ? s0.len : wl, rs};
-    const ChainView V{S, a, b, s0.off, s0.len};
-    const Tunnel T = decode_tunnel_chain(L, dw, V, flags);
-    if (T.ok) {
-        parse_inner_lane(dw, V, T, flags, L);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 20; ++k) L.w[k] = 0u;
-        L.w[0] = RPKT_S_NO_INNER;
-        L.want_l4 = false;
-        L.stream_s = L.stream_e = 0u;
-    }
+    const ChainView V = chain_view(W, lane, s0, S, a, b, rs);
+    const Tunnel T = decode_tunnel(L, V, flags);
+    if (T.ok) parse_inner_lane(V, T, flags, L);
+    else no_inner(L);
     stage_record(W, lane, L.w);
 
     // 3. L4 bytes past the window: the inner range (the outer one when there is no inner
@@ -443,8 +245,7 @@ void tunnel_chains_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
     }
     flush_stage(rec_stage(W), lane, inner, p0, n);
     flush_stage(scratch.outer, lane, outer, p0, n);
-    if (valid) __builtin_nontemporal_store(u32x4{T.w[0], T.w[1], T.w[2], T.w[3]},
-                                           reinterpret_cast<u32x4*>(tun) + i);
+    if (valid) store_tun(tun, i, T);
 }
 
 }  // namespace

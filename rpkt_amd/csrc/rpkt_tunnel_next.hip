@@ -74,14 +74,12 @@ void tunnel_next_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         for (int k = 0; k < 20; ++k) L.w[k] = rl[k];
     }
     wave_sync();                                     // every lane has its words: the stage is free
-    // status and is6 from the words (as record_event); a frame without a level-k inner
-    // frame gets a status that dispatches to nothing
-    L.status = have ? L.w[0] & 0xffu : (uint32_t)RPKT_S_ETH_SHORT;
-    {
-        const uint32_t nv = (L.w[0] >> 8) & 0xffu;
-        const uint32_t det = nv == 0u ? L.w[0] >> 16 : (nv == 1u ? L.w[5] & 0xffffu : L.w[5] >> 16);
-        L.is6 = det == 0x86ddu && L.status != RPKT_S_ETH_SHORT && L.status != RPKT_S_VLAN_SHORT &&
-                L.status != RPKT_S_NOT_IPV4;
+    // status and is6 from the words; a frame without a level-k inner frame gets a status
+    // that dispatches to nothing
+    rec_status_is6(L.w, L.status, L.is6);
+    if (!have) {
+        L.status = RPKT_S_ETH_SHORT;
+        L.is6 = false;
     }
     const uint32_t k_off = tw.y & 0xffffu, k_len = L.w[19];       // level k: inner_off, frame_len
 
@@ -91,7 +89,7 @@ void tunnel_next_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
     const SpanSrc spans{offsets, stride, frame_len, fb, n};
     const Frame fr = spans.get(i);
-    Tunnel T = decode_tunnel(L, FrameDw{W.win, (uint32_t)kWin, fr.off, fb, rs}, flags);
+    Tunnel T = decode_tunnel(L, FlatView{{W.win, (uint32_t)kWin, fr.off, fb, rs}}, flags);
 
     // 3. no tunnel in the tile: its NONE / NO_INNER records, no frame byte read
     if (__ballot((T.w[0] & 0xffu) != RPKT_TUN_NONE) == 0) {       // wave-uniform
@@ -103,8 +101,7 @@ void tunnel_next_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
             const u32x4 v = {c % 5 == 0 ? (uint32_t)RPKT_S_NO_INNER : 0u, 0u, 0u, 0u};
             if (c / 5 < nrec) __builtin_nontemporal_store(v, &out[c]);
         }
-        if (valid) __builtin_nontemporal_store(u32x4{T.w[0], T.w[1], T.w[2], T.w[3]},
-                                               reinterpret_cast<u32x4*>(tun_next) + i);
+        if (valid) store_tun(tun_next, i, T);
         return;
     }
 
@@ -125,13 +122,7 @@ void tunnel_next_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         wave_sync();
     }
     parse_lane(W, lane, fi, T.ok, flags, L, rs, fb, T.start_et, is);
-    if (!T.ok) {
-#pragma unroll
-        for (int k = 0; k < 20; ++k) L.w[k] = 0u;
-        L.w[0] = RPKT_S_NO_INNER;
-        L.want_l4 = false;
-        L.stream_s = L.stream_e = 0u;
-    }
+    if (!T.ok) no_inner(L);
     stage_record(W, lane, L.w);
 
     // 5. the innermost L4 bytes past the window
@@ -145,8 +136,7 @@ void tunnel_next_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
     if ((flags & RPKT_F_FLOW_EV) && valid && T.ok)
         __builtin_nontemporal_store(record_event(rec_stage(W) + lane * 21, n_buckets), &flow_ev[i]);
     flush_stage(rec_stage(W), lane, inner_next, p0, n);
-    if (valid) __builtin_nontemporal_store(u32x4{T.w[0], T.w[1], T.w[2], T.w[3]},
-                                           reinterpret_cast<u32x4*>(tun_next) + i);
+    if (valid) store_tun(tun_next, i, T);
 }
 
 }  // namespace

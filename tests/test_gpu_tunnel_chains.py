@@ -120,6 +120,21 @@ def test_captures_cut_at_every_position(torch):
     assert len(np.unique(t["status"])) >= 5
 
 
+def test_inner_ip6_extension_headers_cut_at_every_position(torch):
+    """VXLAN, GTP-U and GRE around an inner IPv6/UDP packet with a hop-by-hop header, a
+    routing header (the pseudo header's final destination) and destination options plus a
+    fragment header, as two-segment chains cut at every position 1..len-1 (about 1,800 chains
+    in one launch): the IPv6 extension walk on an inner packet, every header in or past
+    segment 0's window, whole or cut.  test_tunnel_chain_model.py pins the uncut frames."""
+    frames, lens = [], []
+    for f in tf.inner_ip6_ext_frames():
+        for c in range(1, len(f)):
+            frames.append(f)
+            lens.append([c, len(f) - c])
+    o, t, i = check(model.lay_out(frames, lens), F6)
+    assert (i["status"] == 0).sum() >= 9 * 62     # at least the cuts in the 62 data bytes
+
+
 def test_captures_in_tiny_segments(torch):
     """[2] * k and [1] * len chains: the many-items path of the chain stream."""
     frames, lens = [], []

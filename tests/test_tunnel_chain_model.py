@@ -10,7 +10,7 @@ import pytest
 
 from oracle import oracle
 from rpkt_amd import gen
-from rpkt_amd.records import F_IPV6, STATUS, TUN_KIND, TUN_STATUS
+from rpkt_amd.records import F_IPV6, STATUS, TUN_KIND, TUN_STATUS, ip6_block
 
 import tunnel_chain_model as model
 import tunnel_frames as tf
@@ -136,3 +136,19 @@ def test_gtp_packet_len_is_tested_against_remaining_not_chunk():
     pb = model.Pbuf(hc.buf, hc.segs, hc.chain_first, 0)
     assert pb.chunk_len(ts, ts + plen) == 12 < plen
     same(run(hc, 3), flat([f, f], 3))
+
+
+def test_inner_ip6_extension_headers_equal_the_flat_oracle():
+    """The frames of test_gpu_tunnel_chains.py's every-cut sweep, uncut: the model is the
+    flat oracle, every tunnel decodes, and every inner record is an IPv6 one whose parse
+    went through the extension walk."""
+    frames = tf.inner_ip6_ext_frames()
+    assert len(frames) == 9
+    got = run(model.lay_out(frames, [[len(f)] for f in frames]), F6)
+    same(got, flat(frames, F6))
+    o, t, i = got
+    assert (t["status"] == TUN_STATUS["OK"]).all()
+    assert sorted(t["kind"]) == sorted([TUN_KIND["VXLAN"], TUN_KIND["GTPU"], TUN_KIND["GRE"]] * 3)
+    assert (i["status"] == STATUS["OK"]).all()
+    assert (ip6_block(i)["ip6_n_ext"] >= 1).all() and (ip6_block(i)["ip_protocol"] == 17).all()
+    assert (i["l4_sum"] == 0xffff).all()          # the routing header's final destination too

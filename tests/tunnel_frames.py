@@ -89,6 +89,38 @@ def gre(inner, proto=0x0800, checksum=False, key=None):
     return bytes(pkt)
 
 
+def ipv6_ext_udp(exts, data, final_dst=None, src=b"\xfd\x00" + bytes(13) + b"\x01",
+                 dst=b"\xfd\x00" + bytes(13) + b"\x02"):
+    """IPv6 / extension headers [(type, bytes after the next-header and length bytes)] / UDP,
+    the UDP checksum over the pseudo header with final_dst (a routing header's last address)."""
+    u = bytearray(udp(5000, 53, data))
+    ps = src + (final_dst or dst) + struct.pack("!I", len(u)) + b"\0\0\0\x11"
+    u[6:8] = struct.pack("!H", rfc1071(ps + bytes(u)) or 0xffff)
+    body, types = b"", [t for t, _ in exts] + [17]
+    for k, (t, rest) in enumerate(exts):
+        assert t == 44 and len(rest) == 6 or (len(rest) + 2) % 8 == 0
+        body += bytes([types[k + 1], 0 if t == 44 else (len(rest) + 2) // 8 - 1]) + rest
+    return ipv6_packet(types[0], body + bytes(u), src=src, dst=dst)
+
+
+def inner_ip6_ext_frames():
+    """Nine frames of about 200 bytes: VXLAN, GTP-U and GRE, each around an inner IPv6/UDP
+    packet with one hop-by-hop header, with a type-0 routing header (segments_left 2, two
+    addresses) and with destination options before a first-fragment header (offset 0, no
+    more fragments: the packet is whole)."""
+    a1, a2 = b"\xfd\x00" + bytes(13) + b"\x07", b"\xfd\x00" + bytes(13) + b"\x09"
+    data = bytes((k * 5 + 1) & 0xff for k in range(62))
+    inners = [ipv6_ext_udp([(0, b"\x01\x04\0\0\0\0")], data),
+              ipv6_ext_udp([(43, b"\x00\x02\0\0\0\0" + a1 + a2)], data, final_dst=a2),
+              ipv6_ext_udp([(60, b"\x01\x04\0\0\0\0"), (44, b"\0\0\x12\x34\x56\x78")], data)]
+    out = []
+    for p in inners:
+        out.append(ether(0x0800, ipv4_packet(17, udp(40000, 4789, vxlan(ether(0x86dd, p))))))
+        out.append(ether(0x0800, ipv4_packet(17, udp(2152, 2152, gtpu(p, seq=9)))))
+        out.append(ether(0x0800, ipv4_packet(47, gre(p, proto=0x86dd, key=11))))
+    return out
+
+
 def odd_frames(seed=0, n=64):
     """A list of frames: outer IPv6 / VLAN-tagged, long GTP extension chains, GRE over IPv6,
     and random cuts and byte flips of them."""
