@@ -445,6 +445,29 @@ pub unsafe fn segment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mss
                                       out.totals_dev, workspace_dev, stream))
 }
 
+/// rpkt_gpu_segment_chains_workspace_bytes: the workspace of segment_chains for `n_chains`.
+pub fn segment_chains_workspace_bytes(n_chains: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_segment_chains_workspace_bytes(n_chains) }
+}
+
+/// rpkt_gpu_segment_chains: TCP segmentation (TSO) of parsed mbuf chains at `mss` (1..65535),
+/// read in place.  `out` is what segment_batch writes for the chains' bytes in order: a
+/// packed, flat batch of wire frames (`seg_first_dev` has `n_chains + 1` entries).
+///
+/// # Safety
+/// `chains` must describe device memory valid for the call; `recs_dev` must be the records
+/// parse_chains wrote for these same chains; every pointer of `out` must be device memory of
+/// the size its field documents, and `workspace_dev` must hold
+/// `segment_chains_workspace_bytes(chains.n_chains)` bytes (16-byte aligned), all on the same
+/// device.
+pub unsafe fn segment_chains(chains: &ffi::rpkt_chains_t, recs_dev: *const Rec, mss: u32,
+                             out: &SegmentOut, workspace_dev: *mut core::ffi::c_void,
+                             stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_segment_chains(chains, recs_dev, mss, 0, out.frames_dev, out.out_bytes,
+                                       out.offsets_dev, out.out_cap, out.seg_first_dev,
+                                       out.totals_dev, workspace_dev, stream))
+}
+
 /// The outputs of rpkt_gpu_coalesce_batch: a packed batch of `out_cap` slots (`frames_dev`,
 /// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first
 /// position of every output (`src_first_dev`, `n + 1` entries), each merged output's segment

@@ -106,6 +106,12 @@ enum rpkt_status {
  *     (E_INVAL); n == 0 (RPKT_OK); NULL frames_dev (E_INVAL); frames_bytes, then out_bytes at
  *     the same limit (E_TOO_LARGE); no layout (E_INVAL); out_cap == 0 (E_INVAL); alignment
  *     (E_ALIGN): recs_dev, out_frames_dev, workspace_dev 16 B, totals_dev 8 B;
+ *   rpkt_gpu_segment_chains: rpkt_gpu_segment_batch's order with the chain entries' checks in
+ *     the batch's place: a NULL chains, recs_dev, output or workspace_dev (E_INVAL); flags other
+ *     than 0, then mss outside 1..65535 (E_INVAL); n_chains == 0 (RPKT_OK); NULL
+ *     chain_first_dev, or with n_segs > 0 NULL buf_dev / segs_dev (E_INVAL); buf_bytes and
+ *     n_segs (E_TOO_LARGE); out_bytes (E_TOO_LARGE); out_cap == 0 (E_INVAL); alignment
+ *     (E_ALIGN): segs_dev and totals_dev 8 B, recs_dev, out_frames_dev, workspace_dev 16 B;
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags other than
  *     RPKT_COALESCE_TRUST_SUMS, then max_payload outside 1..65535 in mss's place.
@@ -761,6 +767,47 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev
                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                            uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                            uint64_t* totals_dev, void* workspace_dev, void* stream);
+
+/* The same over mbuf chains.  The super-frame tso_tx.rs hands to the port is a chain
+ * (Mbuf::from_slice splits 4000 bytes over 2048-byte data rooms, mbuf.rs:261-312; the port
+ * has the multi-segment offload, tx_offloads bit 15), and so is every jumboframe_tx.rs frame:
+ * anything larger than one data room.  rpkt_gpu_segment_chains reads the chains in place --
+ * no gather into a flat batch first -- and writes wire frames, which are linear by nature.
+ *
+ * Let F_p be chain p's bytes in order under rpkt_chains_t's clamps (a = min(chain_first[p],
+ * n_segs), b = min(max(chain_first[p+1], a), n_segs), each segment clamped to buf_bytes, empty
+ * segments contributing nothing).  Every output -- out_frames_dev, out_offsets_dev,
+ * seg_first_dev, totals_dev -- is byte for byte what rpkt_gpu_segment_batch writes for the
+ * packed batch F_0 .. F_{n_chains-1} with the same recs_dev, mss, out_cap and out_bytes: the
+ * overflow contract, the spare offset slots, nothing written outside the buffers, and the
+ * pass-through of every chain that is not segmented as a copy of [0, pkt_len).
+ *   Records   recs_dev are normally rpkt_gpu_parse_chains' records of these chains: their
+ *             offsets are logical positions in F_p already.  A header that straddles a
+ *             segment boundary is a parse error there, so such a chain passes through.  The
+ *             entry itself puts no condition on where segments are cut: with records that say
+ *             "segment this" (a parse of the flattened bytes), the header [0, payload_off) and
+ *             the payload are gathered across any cuts.
+ *   Nesting   pkt_len, the sum of the clamped segment lengths, takes frame_len's place in
+ *             the nesting test and in the payload_len clamp.
+ *   Overlap   segments may overlap or be shared between chains: the arena is only read.
+ *   Huge      pkt_len is summed in 64 bits for totals_dev; a chain of 4 GiB or more cannot
+ *             fit out_bytes, so the call ends as an overflow.
+ *   Faults    every arena load goes through the buffer resource over [buf_dev, + buf_bytes)
+ *             and every store through one over the output: wrong records give wrong frames,
+ *             never a fault.
+ *   Limits    no cap on the segments of a chain (many tiny segments are slow, not wrong).
+ * flags: 0 (reserved for UDP segmentation).  workspace_dev:
+ * rpkt_gpu_segment_chains_workspace_bytes(n_chains) bytes, 16-byte aligned; calls that share
+ * one must be ordered.  No host step: rpkt_gpu_parse_chains -> rpkt_gpu_segment_chains ->
+ * rpkt_gpu_parse_batch over out_cap slots captures as one graph.
+ * Bounds for sizing: rpkt_gpu_segment_batch's with the sum of the chains' pkt_len in
+ * frames_bytes' place; that sum is at most buf_bytes when segments do not overlap.
+ * Not covered: coalescing over chains, UDP, the inner TCP of tunnelled frames. */
+size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n_chains);
+int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_dev, uint32_t mss,
+                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
+                            uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
+                            uint64_t* totals_dev, void* workspace_dev, void* stream);
 
 /* ---- TCP receive coalescing (GRO / LRO) ------------------------------------------- */
 

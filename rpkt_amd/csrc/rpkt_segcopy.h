@@ -192,18 +192,20 @@ __device__ __forceinline__ uint32_t header_dword(__amdgpu_buffer_rsrc_t rs, uint
     return gdword(rs, fb, s0 + ((d0 & ~3u) + 4u * c - d0));
 }
 
-// Copy the header with the patches applied.  `first`: header_dword of this lane's first
-// dword (c = lane), which the caller loaded along with the payload.
-__device__ __forceinline__ void wave_copy_header(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
-                                                 __amdgpu_buffer_rsrc_t ro, uint32_t s0,
-                                                 uint32_t d0, uint32_t len, uint32_t first,
-                                                 const SegPatch (&P)[kSegPatches], int lane) {
+// Copy a `len`-byte header to [d0, d0 + len) with the patches applied.  fetch(c): the source
+// bytes of destination dword c, as header_dword gives them; `first`: fetch(lane), which the
+// caller loaded along with the payload.
+template <class Fetch>
+__device__ __forceinline__ void wave_copy_header_from(__amdgpu_buffer_rsrc_t ro, uint32_t d0,
+                                                      uint32_t len, uint32_t first,
+                                                      const SegPatch (&P)[kSegPatches], int lane,
+                                                      Fetch fetch) {
     const uint32_t dend = d0 + len;
     const uint32_t ndw = (dend - (d0 & ~3u) + 3u) >> 2;
     for (uint32_t c = (uint32_t)lane; c < ndw; c += kWave) {
         const uint32_t dd = (d0 & ~3u) + 4u * c;
         const int rel = (int)(dd - d0);                 // header offset of the dword's byte 0
-        uint32_t v = c < (uint32_t)kWave ? first : header_dword(rs, fb, s0, d0, c);
+        uint32_t v = c < (uint32_t)kWave ? first : fetch(c);
 #pragma unroll
         for (int k = 0; k < kSegPatches; ++k) {
 #pragma unroll
@@ -215,6 +217,15 @@ __device__ __forceinline__ void wave_copy_header(__amdgpu_buffer_rsrc_t rs, uint
         }
         store_dword_part(ro, dd, v, rel < 0 ? -rel : 0, dend - dd < 4u ? (int)(dend - dd) : 4);
     }
+}
+
+// The same for a header that lies at [s0, s0 + len) of the frames buffer.
+__device__ __forceinline__ void wave_copy_header(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                 __amdgpu_buffer_rsrc_t ro, uint32_t s0,
+                                                 uint32_t d0, uint32_t len, uint32_t first,
+                                                 const SegPatch (&P)[kSegPatches], int lane) {
+    wave_copy_header_from(ro, d0, len, first, P, lane,
+                          [&](uint32_t c) { return header_dword(rs, fb, s0, d0, c); });
 }
 
 }  // namespace

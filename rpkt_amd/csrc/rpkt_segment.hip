@@ -1,6 +1,7 @@
-// rpkt_segment.hip — rpkt_gpu_segment_batch: TCP segmentation (TSO) of a device-resident
-// batch, the TCP_SEG transmit offload of rpkt-dpdk/examples/tso_tx.rs:128-134 under the
-// Linux tcp_gso_segment / DPDK rte_gso rules (include/rpkt_gpu.h has the semantics).
+// rpkt_segment.hip — rpkt_gpu_segment_batch and rpkt_gpu_segment_chains: TCP segmentation
+// (TSO) of a device-resident batch, flat or in mbuf chains, the TCP_SEG transmit offload of
+// rpkt-dpdk/examples/tso_tx.rs:128-134 under the Linux tcp_gso_segment / DPDK rte_gso rules
+// (include/rpkt_gpu.h has the semantics).
 //
 // The output batch has another frame count and other offsets than the input, so the work
 // is planned from the input and split by the output.  Four launches on the stream, no host
@@ -25,6 +26,17 @@
 // Every load goes through the frames buffer resource and every store through one over
 // [out_frames_dev, + out_bytes); an overflowing batch (totals past the capacities) writes
 // its totals and seg_first and nothing else.
+//
+// Over mbuf chains (rpkt_chains_t) the frame is the chain's bytes in order.  The plan and the
+// write have a kernel of their own there and share everything else, the scan kernels
+// included: the plan's lane walks its chain's segments for pkt_len; the write copies a slice
+// of the logical bytes as one wave copy per segment it touches (their sums add: each is over
+// destination-aligned words) and carries its place in the segment list from one output of a
+// chain to the next.  The header [0, payload_off) is read as a flat frame's when it lies in
+// the chain's first non-empty segment (the mbuf layout, and nearly every chain that
+// rpkt_gpu_parse_chains calls TCP: there a header may start where a segment ends but never
+// straddles an end), and byte by byte through the segment list otherwise, its sums then
+// taken at the logical position's parity.
 #include "rpkt_common.h"
 #include "rpkt_args.h"
 #include "rpkt_segcopy.h"
@@ -51,12 +63,100 @@ inline SegWs seg_ws(void* ws, uint32_t n) {
     return w;
 }
 
-// plan words: 0 frame offset, 1 frame length, 2 l3 | l4 << 16, 3 payload_off | payload_len
-// << 16, 4 IPv4 constant sum | ident << 16, 5 TCP constant sum | be16 of TCP bytes 12..13
-// << 16, 6 seq, 7 bit 0 segmented, bit 1 IPv6
+// plan words: 0 frame offset (chains: the chain's first segment, clamped), 1 frame length
+// (chains: pkt_len), 2 l3 | l4 << 16, 3 payload_off | payload_len << 16, 4 IPv4 constant sum |
+// ident << 16, 5 TCP constant sum | be16 of TCP bytes 12..13 << 16, 6 seq, 7 bit 0 segmented,
+// bit 1 IPv6
 constexpr uint32_t kSegOn = 1u, kSegV6 = 2u;
 
 // ---- 1. plan ---------------------------------------------------------------------------
+
+// What the staged record `w` says about a frame of `len` bytes at `mss`.
+struct SegWhat {
+    bool seg, v6;
+    uint32_t l3, l4, po, pl, pdst;
+};
+__device__ __forceinline__ SegWhat seg_decide(const uint32_t* w, bool valid, uint32_t len,
+                                              uint32_t mss) {
+    const uint32_t w0 = w[0], w5 = w[5], w7 = w[7], w8 = w[8], w16 = w[16], w17 = w[17];
+    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
+    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
+    const bool v6 = det == 0x86ddu;
+    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
+    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
+    // offsets that nest as a parse of this frame leaves them; [po, + pl) inside the frame
+    const bool nest = l4 >= l3 && po >= l4 && po <= len && po - l4 >= 20u && po - l4 <= 60u &&
+                      (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
+    uint32_t pl = w17 >> 16;
+    if (nest && pl > len - po) pl = len - po;
+    const bool seg = valid && status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
+                     (v6 || (frag & 0x3fffu) == 0u) && nest && pl > mss;
+    return SegWhat{seg, v6, l3, l4, po, pl, pdst};
+}
+
+// The header bytes of a flat frame at `off` of the frames buffer: dw(x), header bytes
+// x .. x + 3 as a little-endian dword; sum(a, b), the big-endian RFC 1071 sum of [a, b).
+struct FlatHeader {
+    __amdgpu_buffer_rsrc_t rs;
+    uint32_t fb, off;
+    __device__ __forceinline__ uint32_t dw(uint32_t x) const { return gdword(rs, fb, off + x); }
+    __device__ __forceinline__ uint32_t sum(uint32_t a, uint32_t b) const {
+        return range_be_sum(rs, fb, off + a, off + b);
+    }
+};
+
+// Plan words 2..7 of a segmented frame from its header H: the constants all its segments
+// share.
+template <class Header>
+__device__ __forceinline__ void seg_constants(const Header& H, const SegWhat& s, uint32_t (&p)[8]) {
+    const uint32_t l3 = s.l3, l4 = s.l4, po = s.po;
+    // a field leaves a sum by adding its complement (one's complement arithmetic;
+    // the sums stay positive, so the folded values are the plain sums')
+    uint32_t ipc = 0, pseudo;
+    const uint32_t ip0 = H.dw(l3);
+    uint32_t ident = 0;
+    if (!s.v6) {
+        const uint32_t ip1 = H.dw(l3 + 4u), ip2 = H.dw(l3 + 8u);
+        ident = be16_lo(ip1);
+        ipc = H.sum(l3, l4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ ident) + (0xffffu ^ be16_hi(ip2));
+        pseudo = H.sum(l3 + 12u, l3 + 20u);
+    } else {
+        // the pseudo destination: rpkt_gpu_build_batch's rule
+        const uint32_t pd = (s.pdst >= l3 + 24u && s.pdst + 16u <= l4) ? s.pdst : l3 + 24u;
+        pseudo = H.sum(l3 + 8u, l3 + 24u) + H.sum(pd, pd + 16u);
+    }
+    const uint32_t t1 = H.dw(l4 + 4u), t3 = H.dw(l4 + 12u);
+    const uint32_t t4 = H.dw(l4 + 16u);
+    const uint32_t seq = bswap32(t1), w12 = be16_lo(t3);
+    const uint32_t tcpc = H.sum(l4, po) + pseudo + 6u + (0xffffu ^ (seq >> 16)) +
+                          (0xffffu ^ (seq & 0xffffu)) + (0xffffu ^ w12) + (0xffffu ^ be16_lo(t4));
+    p[2] = l3 | (l4 << 16);
+    p[3] = po | (s.pl << 16);
+    p[4] = fold16(ipc) | (ident << 16);
+    p[5] = fold16(tcpc) | (w12 << 16);
+    p[6] = seq;
+    p[7] = kSegOn | (s.v6 ? kSegV6 : 0u);
+}
+
+// The plan's end: frame i's plan, count and bytes to the workspace, the block's sums to part.
+__device__ __forceinline__ void plan_store(bool valid, uint32_t i, const uint32_t (&p)[8],
+                                           uint64_t cnt, uint64_t bytes, u32x4* __restrict__ plan,
+                                           uint32_t* __restrict__ seg_first,
+                                           uint64_t* __restrict__ obase, uint64_t* __restrict__ part,
+                                           uint64_t* red) {
+    if (valid) {
+        plan[2 * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
+        plan[2 * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
+        seg_first[i] = (uint32_t)cnt;
+        obase[i] = bytes;
+    }
+    uint64_t tc, tb;
+    block_excl_scan2(cnt, bytes, tc, tb, red);
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)blockIdx.x] = tc;
+        part[2 * (size_t)blockIdx.x + 1] = tb;
+    }
+}
 
 __global__ __launch_bounds__(kSegBlock)
 void segment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
@@ -71,81 +171,141 @@ void segment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
     const uint32_t i = p0 + lane;
     const bool valid = i < n;
     uint64_t cnt = 0, bytes = 0;
+    uint32_t p[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 
     if (p0 < n) {                                                 // wave-uniform
         // the tile's records, coalesced through the stage (stride 21 dwords)
         uint32_t* st = stage[wave];
         stage_records_tile(st, recs, p0, n, lane);
-        const uint32_t* w = st + lane * 21;
-        const uint32_t w0 = w[0], w5 = w[5], w7 = w[7], w8 = w[8], w16 = w[16], w17 = w[17];
-        const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
-        const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
-        const bool v6 = det == 0x86ddu;
-        const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
-        const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
-
         const Frame fr = valid ? frame_span(offsets, stride, frame_len, fb, i) : Frame{0u, 0u};
-        // offsets that nest as a parse of this frame leaves them; [po, + pl) inside the frame
-        const bool nest = l4 >= l3 && po >= l4 && po <= fr.len && po - l4 >= 20u &&
-                          po - l4 <= 60u &&
-                          (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
-        uint32_t pl = w17 >> 16;
-        if (nest && pl > fr.len - po) pl = fr.len - po;
-        const bool seg = valid && status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
-                         (v6 || (frag & 0x3fffu) == 0u) && nest && pl > mss;
-        uint32_t p[8] = {fr.off, fr.len, 0u, 0u, 0u, 0u, 0u, 0u};
+        const SegWhat s = seg_decide(st + lane * 21, valid, fr.len, mss);
+        p[0] = fr.off;
+        p[1] = fr.len;
         if (valid) {
             cnt = 1;
             bytes = fr.len;
         }
-        if (seg) {
-            const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
-            const uint32_t a3 = fr.off + l3, a4 = fr.off + l4;
-            cnt = (pl + mss - 1u) / mss;
-            bytes = cnt * po + pl;
-            // a field leaves a sum by adding its complement (one's complement arithmetic;
-            // the sums stay positive, so the folded values are the plain sums')
-            uint32_t ipc = 0, pseudo;
-            const uint32_t ip0 = gdword(rs, fb, a3);
-            uint32_t ident = 0;
-            if (!v6) {
-                const uint32_t ip1 = gdword(rs, fb, a3 + 4u), ip2 = gdword(rs, fb, a3 + 8u);
-                ident = be16_lo(ip1);
-                ipc = range_be_sum(rs, fb, a3, a4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ ident) +
-                      (0xffffu ^ be16_hi(ip2));
-                pseudo = range_be_sum(rs, fb, a3 + 12u, a3 + 20u);
-            } else {
-                // the pseudo destination: rpkt_gpu_build_batch's rule
-                const uint32_t pd = (pdst >= l3 + 24u && pdst + 16u <= l4) ? pdst : l3 + 24u;
-                pseudo = range_be_sum(rs, fb, a3 + 8u, a3 + 24u) +
-                         range_be_sum(rs, fb, fr.off + pd, fr.off + pd + 16u);
+        if (s.seg) {
+            cnt = (s.pl + mss - 1u) / mss;
+            bytes = cnt * s.po + s.pl;
+            seg_constants(FlatHeader{make_rsrc(frames, fb), fb, fr.off}, s, p);
+        }
+    }
+    plan_store(valid, i, p, cnt, bytes, plan, seg_first, obase, part, red);
+}
+
+// The segment table of rpkt_chains_t: segment k = (offset, length), clamped to the arena as
+// the chain parse clamps it.  The table is only read, so it is read through the constant
+// address space: with a wave-uniform k (the write's cursor) the load then stays on the
+// scalar side whatever vector stores surround it, and does not wait for them.
+struct SegTable {
+    const uint32_t* segs;
+    uint32_t fb;
+    __device__ __forceinline__ Frame seg(uint32_t k) const {
+        typedef __attribute__((address_space(4))) const uint32_t* cptr;
+        const cptr p = (cptr)(segs + 2 * (size_t)k);
+        const uint32_t x = p[0], y = p[1];
+        const uint32_t off = x < fb ? x : fb;
+        return Frame{off, y < fb - off ? y : fb - off};
+    }
+};
+
+// The header bytes of a chain whose [0, lim) crosses segments (first segment `a`): each
+// byte through a walk of the segment list, sums at the logical position's parity.
+struct GatheredHeader {
+    SegTable S;
+    __amdgpu_buffer_rsrc_t rs;
+    uint32_t a, n_segs, lim;
+    // logical bytes x .. x + 3 (x may lie before 0, as a wrapped value); bytes outside
+    // [0, lim) read as 0
+    __device__ __forceinline__ uint32_t dw(uint32_t x) const {
+        uint32_t v = 0, cum = 0;
+        for (uint32_t k = a; k < n_segs && cum < lim; ++k) {
+            const Frame s = S.seg(k);
+#pragma unroll
+            for (uint32_t b = 0; b < 4u; ++b) {
+                const uint32_t y = x + b;
+                if (y < lim && y - cum < s.len) v |= gbyte(rs, s.off + (y - cum)) << (8u * b);
             }
-            const uint32_t t1 = gdword(rs, fb, a4 + 4u), t3 = gdword(rs, fb, a4 + 12u);
-            const uint32_t t4 = gdword(rs, fb, a4 + 16u);
-            const uint32_t seq = bswap32(t1), w12 = be16_lo(t3);
-            const uint32_t tcpc = range_be_sum(rs, fb, a4, fr.off + po) + pseudo + 6u +
-                                  (0xffffu ^ (seq >> 16)) + (0xffffu ^ (seq & 0xffffu)) +
-                                  (0xffffu ^ w12) + (0xffffu ^ be16_lo(t4));
-            p[2] = l3 | (l4 << 16);
-            p[3] = po | (pl << 16);
-            p[4] = fold16(ipc) | (ident << 16);
-            p[5] = fold16(tcpc) | (w12 << 16);
-            p[6] = seq;
-            p[7] = kSegOn | (v6 ? kSegV6 : 0u);
+            cum += s.len;
         }
+        return v;
+    }
+    __device__ __forceinline__ uint32_t sum(uint32_t lo, uint32_t hi) const {
+        hi = hi < lim ? hi : lim;
+        uint32_t acc = 0, cum = 0;
+        for (uint32_t k = a; k < n_segs && cum < hi; ++k) {
+            const Frame s = S.seg(k);
+            const uint32_t e = s.len < hi - cum ? cum + s.len : hi;
+            for (uint32_t y = lo > cum ? lo : cum; y < e; ++y)
+                acc += gbyte(rs, s.off + (y - cum)) << (((y - lo) & 1u) ? 0u : 8u);
+            cum += s.len;
+        }
+        return fold16(acc);
+    }
+};
+
+// chain p's first segment and the end of its list, under rpkt_chains_t's clamps
+__device__ __forceinline__ void chain_range(const uint32_t* __restrict__ chain_first,
+                                            uint32_t n_segs, uint32_t p, uint32_t& a, uint32_t& b) {
+    const uint32_t f0 = chain_first[p], f1 = chain_first[p + 1];
+    a = f0 < n_segs ? f0 : n_segs;
+    b = f1 > a ? f1 : a;
+    b = b < n_segs ? b : n_segs;
+}
+
+__global__ __launch_bounds__(kSegBlock)
+void segment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
+                                const uint32_t* __restrict__ segs, uint32_t n_segs,
+                                const uint32_t* __restrict__ chain_first, uint32_t n,
+                                const rpkt_rec_t* __restrict__ recs, uint32_t mss,
+                                u32x4* __restrict__ plan, uint32_t* __restrict__ seg_first,
+                                uint64_t* __restrict__ obase, uint64_t* __restrict__ part) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    uint64_t cnt = 0, bytes = 0;
+    uint32_t p[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+
+    if (p0 < n) {                                                 // wave-uniform
+        uint32_t* st = stage[wave];
+        stage_records_tile(st, recs, p0, n, lane);
+        const SegTable S{segs, fb};
+        // pkt_len in 64 bits (segments may overlap: no bound but n_segs * buf_bytes), and the
+        // first non-empty segment, where the header starts
+        uint32_t a = 0, b = 0;
+        if (valid) chain_range(chain_first, n_segs, i, a, b);
+        uint64_t pkt = 0;
+        Frame s0{fb, 0u};
+        for (uint32_t k = a; k < b; ++k) {
+            const Frame s = S.seg(k);
+            if (pkt == 0) s0 = s;
+            pkt += s.len;
+        }
+        // a chain of 4 GiB or more cannot fit out_bytes: the call overflows and the write
+        // never sees this plan; the record's offsets are 16 bits wide, so saturating is exact
+        const uint32_t len = pkt < 0xffffffffull ? (uint32_t)pkt : 0xffffffffu;
+        const SegWhat s = seg_decide(st + lane * 21, valid, len, mss);
+        p[0] = a;
+        p[1] = len;
         if (valid) {
-            plan[2 * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
-            plan[2 * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
-            seg_first[i] = (uint32_t)cnt;
-            obase[i] = bytes;
+            cnt = 1;
+            bytes = pkt;
+        }
+        if (s.seg) {
+            cnt = (s.pl + mss - 1u) / mss;
+            bytes = cnt * s.po + s.pl;
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
+            if (__builtin_expect(s.po <= s0.len, 1))
+                seg_constants(FlatHeader{rs, fb, s0.off}, s, p);
+            else
+                seg_constants(GatheredHeader{S, rs, a, n_segs, s.po}, s, p);
         }
     }
-    uint64_t tc, tb;
-    block_excl_scan2(cnt, bytes, tc, tb, red);
-    if (threadIdx.x == 0) {
-        part[2 * (size_t)blockIdx.x] = tc;
-        part[2 * (size_t)blockIdx.x + 1] = tb;
-    }
+    plan_store(valid, i, p, cnt, bytes, plan, seg_first, obase, part, red);
 }
 
 // ---- 2. scan ---------------------------------------------------------------------------
@@ -193,6 +353,53 @@ void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
 
 // ---- 3. write --------------------------------------------------------------------------
 
+// Output k of a segmented frame with plan (pa, pb) and output byte base `base`: where it
+// goes and which payload bytes it carries.
+struct SegOut {
+    bool v6, last;
+    uint32_t l3, l4, po, done, pk, d0;
+};
+__device__ __forceinline__ SegOut seg_out(u32x4 pa, u32x4 pb, uint32_t mss, uint32_t k,
+                                          uint32_t base) {
+    SegOut o;
+    o.v6 = (pb.w & kSegV6) != 0u;
+    o.l3 = pa.z & 0xffffu;
+    o.l4 = pa.z >> 16;
+    o.po = pa.w & 0xffffu;
+    const uint32_t pl = pa.w >> 16;
+    o.done = k * mss;                                             // < pl: k < ceil(pl / mss)
+    const uint32_t left = o.done < pl ? pl - o.done : 0u;
+    o.pk = left < mss ? left : mss;
+    o.last = left <= mss;
+    o.d0 = base + k * (o.po + mss);
+    return o;
+}
+
+// The fields output k's header differs in, `pay` the big-endian sum of its payload.
+__device__ __forceinline__ void seg_patches(const SegOut& o, u32x4 pb, uint32_t k, uint32_t pay,
+                                            SegPatch (&P)[kSegPatches]) {
+    const uint32_t l3 = o.l3, l4 = o.l4, po = o.po, pk = o.pk;
+    if (!o.v6) {
+        const uint32_t tot = po - l3 + pk, ident = ((pb.x >> 16) + k) & 0xffffu;
+        const uint32_t ck = ~fold16((pb.x & 0xffffu) + tot + ident) & 0xffffu;
+        P[0] = SegPatch{l3 + 2u, 4u, bswap16(tot) | (bswap16(ident) << 16)};
+        P[1] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
+    } else {
+        P[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + pk) & 0xffffu)};
+        P[1] = SegPatch{0u, 0u, 0u};
+    }
+    const uint32_t seq = pb.z + o.done;
+    uint32_t w12 = pb.y >> 16;
+    if (!o.last) w12 &= ~0x09u;                                   // FIN, PSH: the last segment's
+    if (k != 0u) w12 &= ~0x80u;                                   // CWR: the first segment's
+    const uint32_t tlen = po - l4 + pk;
+    const uint32_t tck = ~fold16((pb.y & 0xffffu) + (seq >> 16) + (seq & 0xffffu) + w12 + tlen + pay) &
+                         0xffffu;
+    P[2] = SegPatch{l4 + 4u, 4u, bswap32(seq)};
+    P[3] = SegPatch{l4 + 13u, 1u, w12 & 0xffu};
+    P[4] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
+}
+
 // Output j, the k-th of the input frame with plan (pa, pb) and output byte base `base`: its
 // offset entry and its bytes, the whole wave.
 __device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
@@ -206,41 +413,16 @@ __device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t
         wave_copy<false>(rs, fb, ro, foff, base, flen, lane);
         return;
     }
-    const bool v6 = (pb.w & kSegV6) != 0u;
-    const uint32_t l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu, pl = pa.w >> 16;
-    const uint32_t done = k * mss;                                // < pl: k < ceil(pl / mss)
-    const uint32_t left = done < pl ? pl - done : 0u;
-    const uint32_t pk = left < mss ? left : mss;
-    const bool last = left <= mss;
-    const uint32_t d0 = base + k * (po + mss);
-    if (lane == 0) out_offsets[j + 1] = d0 + po + pk;
+    const SegOut o = seg_out(pa, pb, mss, k, base);
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.po + o.pk;
     // the payload slice first: its sum goes into the header, whose bytes are fetched along
     // with it (a lane past the header reads a dword it does not keep)
-    const uint32_t hfirst = header_dword(rs, fb, foff, d0, (uint32_t)lane);
-    const uint32_t part = wave_copy<true>(rs, fb, ro, foff + po + done, d0 + po, pk, lane);
-    const uint32_t pay = be_sum(wave_sum(fold16(part)), d0 + po);
-
+    const uint32_t hfirst = header_dword(rs, fb, foff, o.d0, (uint32_t)lane);
+    const uint32_t part = wave_copy<true>(rs, fb, ro, foff + o.po + o.done, o.d0 + o.po, o.pk, lane);
+    const uint32_t pay = be_sum(wave_sum(fold16(part)), o.d0 + o.po);
     SegPatch P[kSegPatches];
-    if (!v6) {
-        const uint32_t tot = po - l3 + pk, ident = ((pb.x >> 16) + k) & 0xffffu;
-        const uint32_t ck = ~fold16((pb.x & 0xffffu) + tot + ident) & 0xffffu;
-        P[0] = SegPatch{l3 + 2u, 4u, bswap16(tot) | (bswap16(ident) << 16)};
-        P[1] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
-    } else {
-        P[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + pk) & 0xffffu)};
-        P[1] = SegPatch{0u, 0u, 0u};
-    }
-    const uint32_t seq = pb.z + done;
-    uint32_t w12 = pb.y >> 16;
-    if (!last) w12 &= ~0x09u;                                     // FIN, PSH: the last segment's
-    if (k != 0u) w12 &= ~0x80u;                                   // CWR: the first segment's
-    const uint32_t tlen = po - l4 + pk;
-    const uint32_t tck = ~fold16((pb.y & 0xffffu) + (seq >> 16) + (seq & 0xffffu) + w12 + tlen + pay) &
-                         0xffffu;
-    P[2] = SegPatch{l4 + 4u, 4u, bswap32(seq)};
-    P[3] = SegPatch{l4 + 13u, 1u, w12 & 0xffu};
-    P[4] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
-    wave_copy_header(rs, fb, ro, foff, d0, po, hfirst, P, lane);
+    seg_patches(o, pb, k, pay, P);
+    wave_copy_header(rs, fb, ro, foff, o.d0, o.po, hfirst, P, lane);
 }
 
 // A wave writes kSegRun consecutive outputs.  What precedes an output's first copy load is a
@@ -253,24 +435,24 @@ __device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t
 #endif
 constexpr uint32_t kSegRun = RPKT_SEG_RUN;
 
-__global__ __launch_bounds__(kSegBlock)
-void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n, uint32_t mss,
-                          const u32x4* __restrict__ plan, const uint32_t* __restrict__ seg_first,
-                          const uint64_t* __restrict__ obase, const uint64_t* __restrict__ totals,
-                          uint8_t* __restrict__ out, uint32_t out_bytes,
-                          uint32_t* __restrict__ out_offsets, uint32_t out_cap) {
-    const int lane = threadIdx.x & (kWave - 1);
+// The wave's run of outputs [j0, jend) and the input frame i of output j0; false when the
+// wave has nothing to write (past out_cap, an overflowing batch, only spare slots, whose
+// offsets it fills).  Wave-uniform throughout.
+__device__ __forceinline__ bool output_run(uint32_t n, const uint32_t* __restrict__ seg_first,
+                                           const uint64_t* __restrict__ totals, uint32_t out_bytes,
+                                           uint32_t* __restrict__ out_offsets, uint32_t out_cap,
+                                           int lane, uint32_t& j0, uint32_t& jend, uint32_t& i) {
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t j64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kSegRun;
-    if (j64 >= out_cap) return;                                   // wave-uniform, as all below
-    const uint32_t j0 = (uint32_t)j64;
+    if (j64 >= out_cap) return false;
+    j0 = (uint32_t)j64;
     const uint32_t j1 = out_cap - j0 < kSegRun ? out_cap : j0 + kSegRun;   // outputs [j0, j1)
     const uint64_t n_out = totals[0], need = totals[1];
-    if (n_out > out_cap || need > out_bytes) return;              // overflow: the totals say so
+    if (n_out > out_cap || need > out_bytes) return false;        // overflow: the totals say so
     // spare slots are empty frames at the end
     if ((uint32_t)lane < j1 - j0 && j0 + (uint32_t)lane >= n_out)
         out_offsets[j0 + (uint32_t)lane + 1u] = (uint32_t)need;
-    if (j0 >= n_out) return;
+    if (j0 >= n_out) return false;
     if (j0 == 0u && lane == 0) out_offsets[0] = 0u;
     // the input frame of output j0: the last i with seg_first[i] <= j0 (every frame has an
     // output, so i <= j0).  64 probes a round, one per lane: three dependent loads at
@@ -284,12 +466,25 @@ void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
         lo += c * step;
         hi = hi - lo < step - 1u ? hi : lo + step - 1u;
     }
-    uint32_t i = lo, cur = seg_first[i], nxt = seg_first[i + 1];
+    i = lo;
+    jend = j1 < n_out ? j1 : (uint32_t)n_out;
+    return true;
+}
+
+__global__ __launch_bounds__(kSegBlock)
+void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n, uint32_t mss,
+                          const u32x4* __restrict__ plan, const uint32_t* __restrict__ seg_first,
+                          const uint64_t* __restrict__ obase, const uint64_t* __restrict__ totals,
+                          uint8_t* __restrict__ out, uint32_t out_bytes,
+                          uint32_t* __restrict__ out_offsets, uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t j0, jend, i;
+    if (!output_run(n, seg_first, totals, out_bytes, out_offsets, out_cap, lane, j0, jend, i)) return;
+    uint32_t cur = seg_first[i], nxt = seg_first[i + 1];
     u32x4 pa = plan[2 * (size_t)i], pb = plan[2 * (size_t)i + 1];
     uint32_t base = (uint32_t)obase[i];                           // < need <= out_bytes < 4 GiB
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
-    const uint32_t jend = j1 < n_out ? j1 : (uint32_t)n_out;
     for (uint32_t j = j0; j < jend; ++j) {
         if (j >= nxt) {                                           // the next frame's first output
             while (j >= nxt && i + 1u < n) {
@@ -303,6 +498,138 @@ void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
         }
         write_output(rs, fb, ro, out_offsets, mss, j, j - cur, pa, pb, base, lane);
     }
+}
+
+// A wave's place in a chain's segment list: segment k starts at logical byte `cum`.  The
+// values are wave-uniform, so the segment table is read on the scalar side.
+struct ChainCursor {
+    uint32_t k, cum;
+};
+
+// Copy logical bytes [pos, pos + len) of the chain under the cursor (pos >= c.cum) to the
+// output at d, one wave copy per segment they touch; the cursor moves to the segment that
+// holds the slice's end.  Pieces that meet inside a 16-B destination chunk write disjoint
+// bytes, and each piece's sum is over destination-aligned words, so the sums add.
+template <bool SUM>
+__device__ __forceinline__ uint32_t chain_copy(__amdgpu_buffer_rsrc_t rs, const SegTable& S,
+                                               uint32_t n_segs, __amdgpu_buffer_rsrc_t ro,
+                                               ChainCursor& c, uint32_t pos, uint32_t d,
+                                               uint32_t len, int lane) {
+    uint32_t acc = 0;
+    while (len != 0u && c.k < n_segs) {
+        const Frame s = S.seg(c.k);
+        const uint32_t in = pos - c.cum;
+        if (in >= s.len) {                                        // pos is past this segment
+            c.cum += s.len;
+            ++c.k;
+            continue;
+        }
+        const uint32_t take = s.len - in < len ? s.len - in : len;
+        acc += wave_copy<SUM>(rs, S.fb, ro, s.off + in, d, take, lane);
+        pos += take;
+        d += take;
+        len -= take;
+    }
+    return acc;
+}
+
+// The chain a wave is writing outputs of: its plan, its output byte base, the cursor, and
+// where the header is (hdr: the first non-empty segment's offset when [0, payload_off) lies
+// in it, `flat`).
+struct ChainState {
+    u32x4 pa, pb;
+    uint32_t base, hdr;
+    bool flat;
+    ChainCursor c;
+};
+__device__ __forceinline__ ChainState chain_state(const u32x4* __restrict__ plan,
+                                                  const uint64_t* __restrict__ obase, uint32_t i,
+                                                  const SegTable& S, uint32_t n_segs) {
+    ChainState st;
+    st.pa = plan[2 * (size_t)i];
+    st.pb = plan[2 * (size_t)i + 1];
+    st.base = (uint32_t)obase[i];                                 // < need <= out_bytes < 4 GiB
+    st.c = ChainCursor{st.pa.x, 0u};
+    st.hdr = S.fb;
+    st.flat = true;
+    if (st.pb.w & kSegOn) {                     // pkt_len >= payload_off > 0: a segment has bytes
+        Frame s{S.fb, 0u};
+        while (st.c.k < n_segs && (s = S.seg(st.c.k)).len == 0u) ++st.c.k;
+        st.hdr = s.off;
+        st.flat = (st.pa.w & 0xffffu) <= s.len;
+    }
+    return st;
+}
+
+__device__ __forceinline__ void write_chain_output(__amdgpu_buffer_rsrc_t rs, const SegTable& S,
+                                                   uint32_t n_segs, __amdgpu_buffer_rsrc_t ro,
+                                                   uint32_t* __restrict__ out_offsets, uint32_t mss,
+                                                   uint32_t j, uint32_t k, ChainState& st, int lane) {
+    const uint32_t fb = S.fb;
+    if (!(st.pb.w & kSegOn)) {                                    // pass-through: a byte copy
+        if (lane == 0) out_offsets[j + 1] = st.base + st.pa.y;
+        chain_copy<false>(rs, S, n_segs, ro, st.c, 0u, st.base, st.pa.y, lane);
+        return;
+    }
+    const SegOut o = seg_out(st.pa, st.pb, mss, k, st.base);
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.po + o.pk;
+    const GatheredHeader G{S, rs, st.pa.x, n_segs, o.po};
+    const uint32_t hdr = st.hdr, d0 = o.d0;
+    const bool flat = st.flat;                                    // wave-uniform
+    auto fetch = [&](uint32_t c) -> uint32_t {
+        return flat ? header_dword(rs, fb, hdr, d0, c) : G.dw((d0 & ~3u) + 4u * c - d0);
+    };
+    const uint32_t hfirst = fetch((uint32_t)lane);
+    const uint32_t part = chain_copy<true>(rs, S, n_segs, ro, st.c, o.po + o.done, o.d0 + o.po,
+                                           o.pk, lane);
+    const uint32_t pay = be_sum(wave_sum(fold16(part)), o.d0 + o.po);
+    SegPatch P[kSegPatches];
+    seg_patches(o, st.pb, k, pay, P);
+    wave_copy_header_from(ro, o.d0, o.po, hfirst, P, lane, fetch);
+}
+
+__global__ __launch_bounds__(kSegBlock)
+void segment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
+                                 const uint32_t* __restrict__ segs, uint32_t n_segs, uint32_t n,
+                                 uint32_t mss, const u32x4* __restrict__ plan,
+                                 const uint32_t* __restrict__ seg_first,
+                                 const uint64_t* __restrict__ obase,
+                                 const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
+                                 uint32_t out_bytes, uint32_t* __restrict__ out_offsets,
+                                 uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t j0, jend, i;
+    if (!output_run(n, seg_first, totals, out_bytes, out_offsets, out_cap, lane, j0, jend, i)) return;
+    uint32_t cur = seg_first[i], nxt = seg_first[i + 1];
+    const SegTable S{segs, fb};
+    ChainState st = chain_state(plan, obase, i, S, n_segs);
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t j = j0; j < jend; ++j) {
+        if (j >= nxt) {                                           // the next chain's first output
+            while (j >= nxt && i + 1u < n) {
+                ++i;
+                cur = nxt;
+                nxt = seg_first[i + 1];
+            }
+            st = chain_state(plan, obase, i, S, n_segs);
+        }
+        write_chain_output(rs, S, n_segs, ro, out_offsets, mss, j, j - cur, st, lane);
+    }
+}
+
+// the scans and the write's grid, the same for both entries: `n` inputs planned into ws
+template <typename... KArgs, typename... Args>
+int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, uint32_t out_cap,
+                   uint32_t* seg_first_dev, uint64_t* totals_dev, hipStream_t st, Args... args) {
+    const uint32_t nb = seg_blocks(n);
+    RPKT_TRY(launch(segment_scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, n,
+                    seg_first_dev, totals_dev));
+    RPKT_TRY(launch(segment_scan_frames_kernel, dim3(nb), dim3(kSegBlock), 0, st, n, ws.part,
+                    seg_first_dev, ws.obase));
+    const uint64_t per_block = (uint64_t)kWavesPerBlock * kSegRun;        // outputs a block
+    const uint32_t wb = (uint32_t)(((uint64_t)out_cap + per_block - 1) / per_block);
+    return launch(write_kernel, dim3(wb), dim3(kSegBlock), 0, st, args...);
 }
 
 }  // namespace
@@ -331,19 +658,43 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev, ui
         return RPKT_E_ALIGN;
 
     const SegWs ws = seg_ws(workspace_dev, b->n);
-    const uint32_t nb = seg_blocks(b->n);
-    hipStream_t st = (hipStream_t)stream;
     RPKT_TRY(launch_batch(segment_plan_kernel, kSegBlock, 0, stream, *b, recs_dev, mss, ws.plan,
                           seg_first_dev, ws.obase, ws.part));
-    RPKT_TRY(launch(segment_scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, b->n,
-                    seg_first_dev, totals_dev));
-    RPKT_TRY(launch(segment_scan_frames_kernel, dim3(nb), dim3(kSegBlock), 0, st, b->n, ws.part,
-                    seg_first_dev, ws.obase));
-    const uint64_t per_block = (uint64_t)kWavesPerBlock * kSegRun;        // outputs a block
-    const uint32_t wb = (uint32_t)(((uint64_t)out_cap + per_block - 1) / per_block);
-    return launch(segment_write_kernel, dim3(wb), dim3(kSegBlock), 0, st, b->frames_dev,
-                  (uint32_t)b->frames_bytes, b->n, mss, ws.plan, seg_first_dev, ws.obase, totals_dev,
-                  out_frames_dev, (uint32_t)out_bytes, out_offsets_dev, out_cap);
+    return scan_and_write(segment_write_kernel, ws, b->n, out_cap, seg_first_dev, totals_dev,
+                          (hipStream_t)stream, b->frames_dev, (uint32_t)b->frames_bytes, b->n, mss,
+                          ws.plan, seg_first_dev, ws.obase, totals_dev, out_frames_dev,
+                          (uint32_t)out_bytes, out_offsets_dev, out_cap);
+}
+
+size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n_chains) { return seg_ws_bytes(n_chains); }
+
+int rpkt_gpu_segment_chains(const rpkt_chains_t* c, const rpkt_rec_t* recs_dev, uint32_t mss,
+                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
+                            uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
+                            uint64_t* totals_dev, void* workspace_dev, void* stream) {
+    if (!c || any_null(recs_dev, out_frames_dev, out_offsets_dev, seg_first_dev, totals_dev) ||
+        !workspace_dev)
+        return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, 0u));
+    if (mss == 0u || mss > 65535u) return RPKT_E_INVAL;
+    if (c->n_chains == 0) return RPKT_OK;
+    RPKT_TRY(chains_ok(*c));
+    RPKT_TRY(size_ok(out_bytes));
+    if (out_cap == 0u) return RPKT_E_INVAL;
+    if (misaligned(7, c->segs_dev, totals_dev) || misaligned(15, recs_dev, out_frames_dev) ||
+        misaligned(15, (const uint8_t*)workspace_dev))
+        return RPKT_E_ALIGN;
+
+    const uint32_t n = c->n_chains, fb = (uint32_t)c->buf_bytes;
+    const uint32_t* segs = c->segs_dev;
+    const SegWs ws = seg_ws(workspace_dev, n);
+    RPKT_TRY(launch(segment_chains_plan_kernel, dim3(seg_blocks(n)), dim3(kSegBlock), 0,
+                    (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, c->chain_first_dev, n,
+                    recs_dev, mss, ws.plan, seg_first_dev, ws.obase, ws.part));
+    return scan_and_write(segment_chains_write_kernel, ws, n, out_cap, seg_first_dev, totals_dev,
+                          (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, n, mss, ws.plan,
+                          seg_first_dev, ws.obase, totals_dev, out_frames_dev, (uint32_t)out_bytes,
+                          out_offsets_dev, out_cap);
 }
 
 }  // extern "C"

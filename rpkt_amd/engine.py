@@ -83,6 +83,9 @@ ABI = {
     "rpkt_gpu_segment_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_segment_batch": (_i, [_B, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
                                     _p]),
+    "rpkt_gpu_segment_chains_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_segment_chains": (_i, [_C, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
+                                     _p]),
     "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p, _p]),
@@ -591,6 +594,35 @@ def segment_workspace(n, device="cuda"):
     return _bytes(max(int(lib().rpkt_gpu_segment_workspace_bytes(n)), 16), 1, device)
 
 
+def _segment(name, src, what, recs, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
+             totals, workspace, stream, header_max):
+    """segment_batch and segment_chains: `src` (a DeviceBatch or DeviceChains) cut at `mss`
+    into a packed DeviceBatch; the default sizes from the documented bound over src's bytes."""
+    torch = _torch()
+    dev = src.frames.device
+    n, fbytes = src.n, src.frames.numel()
+    if out_cap is None:
+        out_cap = out_offsets.numel() - 1 if out_offsets is not None else n + fbytes // mss
+    if out_bytes is None:
+        out_bytes = out_frames.numel() if out_frames is not None else \
+            fbytes + (out_cap - n) * (134 if header_max is None else header_max)
+    if out_frames is None:
+        out_frames = _bytes(max(out_bytes, 16), 1, dev)
+    if out_offsets is None:
+        out_offsets = torch.empty(out_cap + 1, dtype=torch.int32, device=dev)
+    if out_frames.numel() < out_bytes or out_offsets.numel() < out_cap + 1:
+        raise RpktError("%s: outputs smaller than out_bytes / out_cap + 1" % what)
+    seg_first = torch.empty(n + 1, dtype=torch.int32, device=dev) if seg_first is None else seg_first
+    totals = torch.empty(2, dtype=torch.int64, device=dev) if totals is None else totals
+    workspace = segment_workspace(n, dev) if workspace is None else workspace
+    if recs.numel() != n * REC_BYTES or seg_first.numel() < n + 1:
+        raise RpktError("%s: records or seg_first do not fit %d frames" % (what, n))
+    _call(name, ctypes.byref(src.desc()), recs.data_ptr(), mss, 0, out_frames.data_ptr(), out_bytes,
+          out_offsets.data_ptr(), out_cap, seg_first.data_ptr(), totals.data_ptr(),
+          workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
+
+
 def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=None,
                   out_bytes=None, seg_first=None, totals=None, workspace=None, stream=None,
                   header_max=None):
@@ -604,29 +636,29 @@ def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=N
     frames_bytes // mss slots and out_bytes = frames_bytes + (out_cap - n) * header_max bytes,
     header_max (the longest payload_off of the batch) 134 unless given: Ethernet, two tags and
     60-B IPv4 and TCP headers; give it for IPv6 frames with long extension chains."""
-    torch = _torch()
-    dev = batch.frames.device
-    n, fbytes = batch.n, batch.frames.numel()
-    if out_cap is None:
-        out_cap = out_offsets.numel() - 1 if out_offsets is not None else n + fbytes // mss
-    if out_bytes is None:
-        out_bytes = out_frames.numel() if out_frames is not None else \
-            fbytes + (out_cap - n) * (134 if header_max is None else header_max)
-    if out_frames is None:
-        out_frames = _bytes(max(out_bytes, 16), 1, dev)
-    if out_offsets is None:
-        out_offsets = torch.empty(out_cap + 1, dtype=torch.int32, device=dev)
-    if out_frames.numel() < out_bytes or out_offsets.numel() < out_cap + 1:
-        raise RpktError("segment_batch: outputs smaller than out_bytes / out_cap + 1")
-    seg_first = torch.empty(n + 1, dtype=torch.int32, device=dev) if seg_first is None else seg_first
-    totals = torch.empty(2, dtype=torch.int64, device=dev) if totals is None else totals
-    workspace = segment_workspace(n, dev) if workspace is None else workspace
-    if recs.numel() != n * REC_BYTES or seg_first.numel() < n + 1:
-        raise RpktError("segment_batch: records or seg_first do not fit %d frames" % n)
-    _call("rpkt_gpu_segment_batch", ctypes.byref(batch.desc()), recs.data_ptr(), mss, 0,
-          out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, seg_first.data_ptr(),
-          totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
-    return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
+    return _segment("rpkt_gpu_segment_batch", batch, "segment_batch", recs, mss, out_frames,
+                    out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max)
+
+
+def segment_chains_workspace(n, device="cuda"):
+    """The workspace tensor of segment_chains for n chains
+    (rpkt_gpu_segment_chains_workspace_bytes)."""
+    return _bytes(max(int(lib().rpkt_gpu_segment_chains_workspace_bytes(n)), 16), 1, device)
+
+
+def segment_chains(chains, recs, mss, out_frames=None, out_offsets=None, out_cap=None,
+                   out_bytes=None, seg_first=None, totals=None, workspace=None, stream=None,
+                   header_max=None):
+    """rpkt_gpu_segment_chains: segment_batch over mbuf chains (a DeviceChains), read in
+    place; `recs` are parse_chains' records of them.  The same return value: (out, seg_first,
+    totals), `out` a packed, flat DeviceBatch of wire frames.
+    The default sizes are segment_batch's with the arena's size, chains.buf.numel(), for
+    frames_bytes: that bounds the chains' bytes only when segments do not overlap and are
+    not shared between chains; size the outputs yourself otherwise."""
+    if workspace is None:
+        workspace = segment_chains_workspace(chains.n, chains.buf.device)
+    return _segment("rpkt_gpu_segment_chains", chains, "segment_chains", recs, mss, out_frames,
+                    out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max)
 
 
 COALESCE_TRUST_SUMS = 1

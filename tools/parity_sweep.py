@@ -15,7 +15,9 @@ and a config 13 / 14 batch), the layer walk; (b) a generator batch of a random c
 build with random checksum flags over its (IPv4 and IPv6) records, the forward with and
 without RPKT_F_IPV6, and the encapsulation build over a tunnel batch (configs 13 / 14); (c)
 a fuzzed mbuf-chain batch (configs 8 / 12) through the chain
-parse, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
+parse, another one through rpkt_gpu_segment_chains at a random mss against
+tests/segment_chains_model.py (the chain parse's records, or the flat oracle's of the
+flattened bytes, which gather headers across the cuts), and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
 random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py; (d)
 a nested tunnel batch (tests/nested_tunnel_ref.py's recipe: config 13 / 14 frames, frame k
 wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level passes
@@ -40,6 +42,8 @@ from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_recor
 
 import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
+import segment_chains_model  # noqa: E402
+import segment_model  # noqa: E402
 import tunnel_chain_model  # noqa: E402
 import tunnel_frames  # noqa: E402
 from test_gpu_parity import assert_same, assert_same16  # noqa: E402
@@ -197,6 +201,29 @@ def check_chains(rng, seed):
     return {"cfg": cfg, "n": int(hc.n), "flags": flags}
 
 
+def check_segment_chains(rng, seed):
+    """rpkt_gpu_segment_chains (frames, offsets, seg_first, totals) against the model."""
+    import torch
+    cfg = int(rng.choice([8, 12]))
+    hc = gen.make_chains(cfg, n=int(rng.integers(1, 6000)), layout="fuzz", seed=seed)
+    mss = int(rng.choice([1, 7, 16, 17, 100, 300, 536, 1448, 65535]))
+    kind = "chain" if rng.random() < 0.6 else "flat"
+    recs = (segment_chains_model.chain_records if kind == "chain" else
+            segment_chains_model.flat_records)(hc)
+    out, first, totals = segment_chains_model.segment_chains(hc, recs, mss)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    out_bytes = int(totals[1]) + int(rng.integers(0, 40))
+    d = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).copy()).cuda()
+    odb, gs, gt = engine.segment_chains(engine.DeviceChains.from_host(hc), d, mss, out_cap=out_cap,
+                                        out_bytes=out_bytes)
+    blob, offs = segment_model.packed_output(out, out_cap)
+    assert gt.cpu().numpy().view(np.uint64).tolist() == totals.tolist(), "segment_chains totals"
+    assert np.array_equal(gs.cpu().numpy().view(np.uint32), first), "segment_chains seg_first"
+    assert np.array_equal(odb.offsets.cpu().numpy().view(np.uint32), offs), "segment_chains offsets"
+    assert np.array_equal(odb.frames.cpu().numpy()[:blob.size], blob), "segment_chains frames"
+    return {"cfg": cfg, "n": int(hc.n), "mss": mss, "records": kind, "n_out": int(totals[0])}
+
+
 def check_tunnel_chains(rng, seed):
     """rpkt_gpu_parse_tunnel_chains (records and flow events) against the model."""
     if rng.random() < 0.7:
@@ -266,6 +293,8 @@ def main():
                 rec["encap"] = check_encap(rng, seed)
                 step = "chains"
                 rec["chains"] = check_chains(rng, seed)
+                step = "segment_chains"
+                rec["segment_chains"] = check_segment_chains(rng, seed)
                 step = "tunnel_chains"
                 rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
                 step = "tunnel_next"

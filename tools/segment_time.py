@@ -18,7 +18,18 @@ The split of the time between plan + scan and write comes from a run of its own:
     rocprofv3 --kernel-trace --stats -d DIR -o seg -- python tools/segment_time.py --trace-launches 6
 
 The run also checks the output: 23 segments a frame, and a parse of it with both sums finds
-every segment OK with valid IPv4 and TCP sums."""
+every segment OK with valid IPv4 and TCP sums.
+
+    python tools/segment_time.py --chains [--out profiles/segment_chains/times.json]
+
+times rpkt_gpu_segment_chains too, in the same interleaved rounds: the same super-frames as
+mbuf chains (gen.make_chains' mbuf layout: 2048-B data rooms in 2176-B slots with 128 B of
+headroom, the slots in a seeded shuffled order; 17 segments a chain, the last one 54 B), the
+records from a parse of the chains.  The yardstick there is what a caller without the entry
+must do, flatten and then segment: segment_batch on the flat batch plus one device copy of
+the bytes (an ideal flatten costs at least that); `chains_over_flatten_then_segment` is
+t(segment_chains) / (t(segment_batch) + t(device_copy)).  The chains' output must equal the
+flat batch's, byte for byte."""
 import argparse
 import json
 import os
@@ -61,15 +72,39 @@ def super_frames(n, seed):
     return f
 
 
+ROOM, HEADROOM = 2048, 128                                        # gen.MBUF_ROOM, MBUF_HEADROOM
+
+
+def mbuf_chains(torch, engine, db, n, seed):
+    """The frames of the strided device batch `db` as DeviceChains in the mbuf layout, built
+    on the device."""
+    flen = HDR + PAYLOAD
+    per = -(-flen // ROOM)
+    rows = torch.zeros((n, per * ROOM), dtype=torch.uint8, device="cuda")
+    rows[:, :flen] = db.frames.view(n, flen)
+    slot = torch.from_numpy(np.random.default_rng(seed).permutation(n * per)).to("cuda")
+    arena = torch.zeros((n * per, ROOM + HEADROOM), dtype=torch.uint8, device="cuda")
+    arena[slot, HEADROOM:] = rows.view(n * per, ROOM)
+    lens = torch.full((n, per), ROOM, dtype=torch.int64, device="cuda")
+    lens[:, per - 1] = flen - (per - 1) * ROOM
+    segs = torch.stack([slot * (ROOM + HEADROOM) + HEADROOM, lens.view(-1)], dim=1)
+    first = torch.arange(n + 1, dtype=torch.int64, device="cuda") * per
+    return engine.DeviceChains(arena.view(-1), segs.to(torch.int32).view(-1).contiguous(),
+                               first.to(torch.int32), n)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/segment/times.json")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--chains", action="store_true",
+                    help="also time rpkt_gpu_segment_chains on the same frames as mbuf chains")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace pass")
     a = ap.parse_args()
+    a.out = a.out or ("profiles/segment_chains/times.json" if a.chains else "profiles/segment/times.json")
     import time
 
     import torch
@@ -101,16 +136,31 @@ def main():
     def copy(k):
         out_frames[:n * flen].copy_(dbs[k % R].frames)
 
+    legs = {"segment_batch": segment, "device_copy": copy}
+    if a.chains:
+        dcs = [mbuf_chains(torch, engine, db, n, seed) for db, seed in zip(dbs, (17, 1717))]
+        crecs = [engine.parse_chains(dc, 0) for dc in dcs]
+        assert all(torch.equal(x, y) for x, y in zip(crecs, recs))
+        chain_out = torch.empty(need, dtype=torch.uint8, device="cuda")
+        chain_offsets, chain_first = torch.empty_like(out_offsets), torch.empty_like(seg_first)
+        chain_totals = torch.zeros_like(totals)
+        cws = engine.segment_chains_workspace(n)
+
+        def segment_chains(k):
+            engine.segment_chains(dcs[k % R], crecs[k % R], MSS, out_frames=chain_out,
+                                  out_offsets=chain_offsets, seg_first=chain_first,
+                                  totals=chain_totals, workspace=cws, stream=stream)
+
+        legs = {"segment_chains": segment_chains, **legs}
     if a.trace_launches:
         for k in range(a.trace_launches):
-            segment(k)
+            (segment_chains if a.chains else segment)(k)
         torch.cuda.synchronize()
         return
-    legs = {"segment_batch": segment, "device_copy": copy}
     k, t_w = 0, time.perf_counter()
     while k < 8 or time.perf_counter() - t_w < 0.3:
-        copy(k)
-        segment(k)
+        for fn in legs.values():
+            fn(k)
         k += 1
         if k % 8 == 0:
             torch.cuda.synchronize()
@@ -142,6 +192,12 @@ def main():
     assert (orec["payload_len"][~last] == MSS).all()
     assert (orec["payload_len"][last] == PAYLOAD - (per - 1) * MSS).all()
 
+    if a.chains:                                                  # the same output from the chains
+        segment_chains(0)
+        torch.cuda.synchronize()
+        assert torch.equal(chain_totals, totals) and torch.equal(chain_first, seg_first)
+        assert torch.equal(chain_offsets, out_offsets) and torch.equal(chain_out, out_frames)
+
     moved = {"frames_in": n * flen, "records_in": n * 80, "frames_out": need,
              "offsets_out": (n_out + 1) * 4}
     alg = sum(moved.values())
@@ -158,6 +214,17 @@ def main():
         2 * n * flen / (med["device_copy"] * 1e-3) / HBM_BYTES_PER_S, 4)
     res["segment_over_copy_per_byte"] = round(
         (med["segment_batch"] / alg) / (med["device_copy"] / (2 * n * flen)), 4)
+    if a.chains:
+        n_segs = dcs[0].segs.numel() // 2
+        res["chains"] = {"room": ROOM, "slot": ROOM + HEADROOM, "segments": n_segs,
+                         "arena_bytes": dcs[0].buf.numel()}
+        calg = alg + n_segs * 8 + (n + 1) * 4
+        res["ms"]["segment_chains"]["bytes"] = calg
+        res["ms"]["segment_chains"]["fraction_of_8TBs"] = round(
+            calg / (med["segment_chains"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        res["chains_over_flatten_then_segment"] = round(
+            med["segment_chains"] / (med["segment_batch"] + med["device_copy"]), 4)
+        res["chains_over_segment_batch"] = round(med["segment_chains"] / med["segment_batch"], 4)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
