@@ -28,11 +28,12 @@
 // sizes (one output of 65,495 one-byte members is 8,187 copy waves, not one wave's loop);
 // its price is the second pass over the merged outputs' headers.  No kernel waits on
 // another workgroup and every loop is bounded by a count from the plan.
+// Shared with rpkt_segment.hip through rpkt_segcopy.h: which records are the TCP frames that
+// segmentation cuts (tcp_where), the record stage, the block scan and launch 5, the copy, the
+// header write, the entry's argument checks and the workspace carving.
 // Every load of frame bytes goes through the frames buffer resource and every store of
 // output bytes through one over [out_frames_dev, + out_bytes); an overflowing call (totals
 // past the capacities) writes its totals, src_first and out_mss and nothing else.
-#include "rpkt_common.h"
-#include "rpkt_args.h"
 #include "rpkt_segcopy.h"
 
 namespace {
@@ -46,25 +47,17 @@ struct CoWs {
     uint32_t* aux;
     uint64_t* part;
     uint32_t* pmax;
+    size_t    bytes;
 };
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-inline uint32_t co_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSegBlock - 1) / kSegBlock); }
-inline size_t co_ws_bytes(uint32_t n) {
-    const size_t nb = co_blocks(n);
-    return (size_t)n * 32u + up16((size_t)n * 8u) + up16((size_t)n * 4u) + nb * 16u + up16(nb * 4u);
-}
 inline CoWs co_ws(void* ws, uint32_t n) {
-    uint8_t* p = static_cast<uint8_t*>(ws);
+    Carve c(ws);
     CoWs w;
-    w.plan = reinterpret_cast<u32x4*>(p);
-    p += (size_t)n * 32u;
-    w.obase = reinterpret_cast<uint64_t*>(p);
-    p += up16((size_t)n * 8u);
-    w.aux = reinterpret_cast<uint32_t*>(p);
-    p += up16((size_t)n * 4u);
-    w.part = reinterpret_cast<uint64_t*>(p);
-    p += (size_t)co_blocks(n) * 16u;
-    w.pmax = reinterpret_cast<uint32_t*>(p);
+    w.plan = c.take<u32x4>(2 * (size_t)n);
+    w.obase = c.take<uint64_t>(n);
+    w.aux = c.take<uint32_t>(n);
+    w.part = c.take<uint64_t>(2 * (size_t)blocks(n));
+    w.pmax = c.take<uint32_t>(blocks(n));
+    w.bytes = c.used();
     return w;
 }
 
@@ -111,20 +104,13 @@ void coalesce_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         }
     }
     const bool present = f < n;
-    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
-    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
-    const bool v6 = det == 0x86ddu;
-    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
-    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
     const Frame fr = present ? frame_span(offsets, stride, frame_len, fb, f) : Frame{0u, 0u};
-    // offsets that nest as segmentation requires them to; [po, + pl) inside the frame
-    const bool nest = l4 >= l3 && po >= l4 && po <= fr.len && po - l4 >= 20u && po - l4 <= 60u &&
-                      (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
-    uint32_t pl = w17 >> 16;
-    if (nest && pl > fr.len - po) pl = fr.len - po;
+    // the frames segmentation cuts, with a payload and sums that verified
+    const TcpWhere s = tcp_where(w0, w5, w7, w8, w16, w17, fr.len);
+    const bool v6 = s.v6;
+    const uint32_t l3 = s.l3, l4 = s.l4, po = s.po, pl = s.pl, pdst = s.pdst;
     const bool sums = trust || ((w18 >> 16) == 0xffffu && (v6 || (w18 & 0xffffu) == 0xffffu));
-    bool elig = present && status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
-                (v6 || (frag & 0x3fffu) == 0u) && nest && pl >= 1u && sums;
+    bool elig = present && s.tcp && pl >= 1u && sums;
     uint32_t seq = 0, idfl = 0, df = 0;
     if (elig) {
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
@@ -296,40 +282,12 @@ void coalesce_group_kernel(uint32_t n, uint32_t max_payload, u32x4* __restrict__
         plan[2 * (size_t)i + 1].w = (ghead ? kCoHead : 0u) | (merged ? kCoMerged : 0u) | (ph << 16);
         obase[i] = bytes;
     }
-    uint64_t tc, tb;
-    block_excl_scan2(cnt, bytes, tc, tb, red);
-    if (threadIdx.x == 0) {
-        part[2 * (size_t)blockIdx.x] = tc;
-        part[2 * (size_t)blockIdx.x + 1] = tb;
-    }
+    block_sums_to_part(cnt, bytes, part, red);
 }
 
 // ---- 5. sums ---------------------------------------------------------------------------
 
-// one block: the block sums -> their exclusive prefixes, kSegBlock at a time with a carry;
-// the totals
-__global__ __launch_bounds__(kSegBlock)
-void coalesce_scan_parts_kernel(uint64_t* __restrict__ part, uint32_t nb,
-                                uint64_t* __restrict__ totals) {
-    __shared__ uint64_t red[2 * kWavesPerBlock];
-    uint64_t ca = 0, cb = 0;
-    for (uint32_t base = 0; base < nb; base += kSegBlock) {
-        const uint32_t k = base + threadIdx.x;
-        uint64_t a = k < nb ? part[2 * (size_t)k] : 0, b = k < nb ? part[2 * (size_t)k + 1] : 0;
-        uint64_t ta, tb;
-        block_excl_scan2(a, b, ta, tb, red);
-        if (k < nb) {
-            part[2 * (size_t)k] = ca + a;
-            part[2 * (size_t)k + 1] = cb + b;
-        }
-        ca += ta;
-        cb += tb;
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = ca;
-        totals[1] = cb;
-    }
-}
+// the block sums' scan: scan_parts_kernel (rpkt_segcopy.h)
 
 // ---- 6. place --------------------------------------------------------------------------
 
@@ -473,8 +431,7 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
             if (!v6) {
                 x = range_be_sum(rs, fb, a3 + 12u, a3 + 20u);
             } else {
-                // the pseudo destination: rpkt_gpu_build_batch's rule
-                const uint32_t pd = (pdst >= l3 + 24u && pdst + 16u <= l4) ? pdst : l3 + 24u;
+                const uint32_t pd = ip6_pseudo_dst(pdst, l3, l4);
                 x = range_be_sum(rs, fb, a3 + 8u, a3 + 24u) +
                     range_be_sum(rs, fb, foff + pd, foff + pd + 16u);
             }
@@ -509,29 +466,19 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
 
 extern "C" {
 
-size_t rpkt_gpu_coalesce_workspace_bytes(uint32_t n) { return co_ws_bytes(n); }
+size_t rpkt_gpu_coalesce_workspace_bytes(uint32_t n) { return co_ws(nullptr, n).bytes; }
 
 int rpkt_gpu_coalesce_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                             const uint32_t* order_dev, uint32_t max_payload, uint32_t flags,
                             uint8_t* out_frames_dev, uint64_t out_bytes, uint32_t* out_offsets_dev,
                             uint32_t out_cap, uint32_t* src_first_dev, uint16_t* out_mss_dev,
                             uint64_t* totals_dev, void* workspace_dev, void* stream) {
-    if (!b || any_null(recs_dev, out_frames_dev, out_offsets_dev, src_first_dev, totals_dev) ||
-        !workspace_dev)
-        return RPKT_E_INVAL;
-    RPKT_TRY(flags_ok(flags, RPKT_COALESCE_TRUST_SUMS));
-    if (max_payload == 0u || max_payload > 65535u) return RPKT_E_INVAL;
+    RPKT_TRY(reframe_args_ok(b, recs_dev, max_payload, flags, RPKT_COALESCE_TRUST_SUMS, out_frames_dev,
+                             out_bytes, out_offsets_dev, out_cap, src_first_dev, totals_dev,
+                             workspace_dev));
     if (b->n == 0) return RPKT_OK;
-    RPKT_TRY(frames_ok(*b));
-    RPKT_TRY(size_ok(b->frames_bytes));
-    RPKT_TRY(size_ok(out_bytes));
-    RPKT_TRY(layout_ok(*b));
-    if (out_cap == 0u) return RPKT_E_INVAL;
-    if (misaligned(15, recs_dev, out_frames_dev) || misaligned(15, (const uint8_t*)workspace_dev) ||
-        misaligned(7, totals_dev))
-        return RPKT_E_ALIGN;
 
-    const uint32_t n = b->n, nb = co_blocks(n), fb = (uint32_t)b->frames_bytes;
+    const uint32_t n = b->n, nb = blocks(n), fb = (uint32_t)b->frames_bytes;
     const CoWs ws = co_ws(workspace_dev, n);
     hipStream_t st = (hipStream_t)stream;
     const dim3 blk(kSegBlock), per(nb);
@@ -542,7 +489,8 @@ int rpkt_gpu_coalesce_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
     RPKT_TRY(launch(coalesce_scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
     RPKT_TRY(launch(coalesce_group_kernel, per, blk, 0, st, n, max_payload, ws.plan, ws.aux, ws.pmax,
                     ws.obase, ws.part));
-    RPKT_TRY(launch(coalesce_scan_parts_kernel, dim3(1), blk, 0, st, ws.part, nb, totals_dev));
+    RPKT_TRY(launch(scan_parts_kernel, dim3(1), blk, 0, st, ws.part, nb, totals_dev,
+                    (uint32_t*)nullptr));
     RPKT_TRY(launch(coalesce_place_kernel, per, blk, 0, st, n, ws.plan, ws.part, totals_dev, ws.obase,
                     src_first_dev, out_mss_dev, out_offsets_dev, out_cap, (uint32_t)out_bytes));
     const uint64_t cper = (uint64_t)kWavesPerBlock * kCoRun;             // positions a block

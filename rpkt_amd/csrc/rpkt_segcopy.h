@@ -1,14 +1,104 @@
-// rpkt_segcopy.h — device code the two units that re-frame a batch share (rpkt_segment.hip:
-// one frame into many; rpkt_coalesce.hip: many into one): a tile's records staged through
-// LDS, header sums by one lane, the block scan of the plan -> scan -> write structure, and
-// the wave copy between any two byte phases that sums what it copies.  Included after
-// rpkt_common.h; everything is inline in an anonymous namespace.
+// rpkt_segcopy.h — what the two units that re-frame a batch share (rpkt_segment.hip: one
+// frame into many; rpkt_coalesce.hip: many into one).  Host: the entries' argument checks and
+// the carving of their workspaces.  Device: what a record says about a TCP frame, a tile's
+// records staged through LDS, header sums by one lane, the block scans of the plan -> scan ->
+// write structure, and the wave copy between any two byte phases that sums what it copies.
+// Everything is inline in an anonymous namespace.
 #pragma once
 #include "rpkt_common.h"
+#include "rpkt_args.h"
 
 namespace {
 
 constexpr int kSegBlock = kWave * kWavesPerBlock;   // frames per block in plan and scan
+
+// The source of a re-framing call, a flat batch or mbuf chains: its input count, its checks
+// with out_bytes' in its documented place, and whether a pointer of its own is misaligned.
+inline uint32_t source_n(const rpkt_batch_t& b) { return b.n; }
+inline uint32_t source_n(const rpkt_chains_t& c) { return c.n_chains; }
+inline int source_ok(const rpkt_batch_t& b, uint64_t out_bytes) {
+    RPKT_TRY(frames_ok(b));
+    RPKT_TRY(size_ok(b.frames_bytes));
+    RPKT_TRY(size_ok(out_bytes));
+    return layout_ok(b);
+}
+inline int source_ok(const rpkt_chains_t& c, uint64_t out_bytes) {
+    RPKT_TRY(chains_ok(c));
+    return size_ok(out_bytes);
+}
+inline bool source_misaligned(const rpkt_batch_t&) { return false; }
+inline bool source_misaligned(const rpkt_chains_t& c) { return misaligned(7, c.segs_dev); }
+
+// The checks of a re-framing entry in the documented order: required pointers, flags, `limit`
+// (mss, max_payload) in 1..65535, no inputs (RPKT_OK: the entry then returns), the source with
+// out_bytes, out_cap, alignment.
+template <class Source>
+inline int reframe_args_ok(const Source* src, const rpkt_rec_t* recs, uint32_t limit,
+                           uint32_t flags, uint32_t allowed, const uint8_t* out_frames,
+                           uint64_t out_bytes, const uint32_t* out_offsets, uint32_t out_cap,
+                           const uint32_t* first, const uint64_t* totals, const void* workspace) {
+    if (!src || any_null(recs, out_frames, out_offsets, first, totals) || !workspace)
+        return RPKT_E_INVAL;
+    RPKT_TRY(flags_ok(flags, allowed));
+    if (limit == 0u || limit > 65535u) return RPKT_E_INVAL;
+    if (source_n(*src) == 0) return RPKT_OK;
+    RPKT_TRY(source_ok(*src, out_bytes));
+    if (out_cap == 0u) return RPKT_E_INVAL;
+    if (source_misaligned(*src) || misaligned(15, recs, out_frames) ||
+        misaligned(15, (const uint8_t*)workspace) || misaligned(7, totals))
+        return RPKT_E_ALIGN;
+    return RPKT_OK;
+}
+
+inline uint32_t blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSegBlock - 1) / kSegBlock); }
+inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+// A workspace handed out in regions rounded up to 16 bytes.  From a null base used() is the
+// size the layout needs: a unit states its layout once, for its pointers and its byte count.
+struct Carve {
+    uintptr_t base, at;
+    explicit Carve(void* ws) : base((uintptr_t)ws), at(base) {}
+    template <class T>
+    T* take(size_t count) {
+        T* r = reinterpret_cast<T*>(at);
+        at += up16(count * sizeof(T));
+        return r;
+    }
+    size_t used() const { return (size_t)(at - base); }
+};
+
+// What the record's dwords 0, 5, 7, 8, 16, 17 say about a frame of `len` bytes: `tcp`, status
+// OK and an unfragmented TCP packet over IPv4 or IPv6 whose offsets nest; pl clamped to the frame.
+struct TcpWhere {
+    bool tcp, v6;
+    uint32_t l3, l4, po, pl, pdst;
+};
+__device__ __forceinline__ TcpWhere tcp_where(uint32_t w0, uint32_t w5, uint32_t w7, uint32_t w8,
+                                              uint32_t w16, uint32_t w17, uint32_t len) {
+    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
+    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
+    const bool v6 = det == 0x86ddu;
+    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
+    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
+    // offsets that nest as a parse of this frame leaves them; [po, + pl) inside the frame
+    const bool nest = l4 >= l3 && po >= l4 && po <= len && po - l4 >= 20u && po - l4 <= 60u &&
+                      (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
+    uint32_t pl = w17 >> 16;
+    if (nest && pl > len - po) pl = len - po;
+    const bool tcp = status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
+                     (v6 || (frag & 0x3fffu) == 0u) && nest;
+    return TcpWhere{tcp, v6, l3, l4, po, pl, pdst};
+}
+// the same from a staged record (stage_records_tile)
+__device__ __forceinline__ TcpWhere tcp_where(const uint32_t* w, uint32_t len) {
+    return tcp_where(w[0], w[5], w[7], w[8], w[16], w[17], len);
+}
+
+// The IPv6 pseudo header's destination: the routing header's final address when ip6_pdst_off
+// lies in [l3 + 24, l4 - 16], else the fixed header's (rpkt_gpu_build_batch's rule, rpkt_tx.hip).
+__device__ __forceinline__ uint32_t ip6_pseudo_dst(uint32_t pdst, uint32_t l3, uint32_t l4) {
+    return (pdst >= l3 + 24u && pdst + 16u <= l4) ? pdst : l3 + 24u;
+}
 
 // the aligned dword at x (bytes past the buffer read as 0: its last, partial dword by bytes)
 __device__ __forceinline__ uint32_t ldw(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t x) {
@@ -90,6 +180,43 @@ __device__ __forceinline__ void block_excl_scan2(uint64_t& a, uint64_t& b, uint6
     __syncthreads();                                   // red is free for the next call
     a = ba + ia - a;
     b = bb + ib - b;
+}
+
+// The end of a planning kernel: the block's sums of (cnt, bytes) to part[blockIdx.x].
+__device__ __forceinline__ void block_sums_to_part(uint64_t cnt, uint64_t bytes,
+                                                   uint64_t* __restrict__ part, uint64_t* red) {
+    uint64_t tc, tb;
+    block_excl_scan2(cnt, bytes, tc, tb, red);
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)blockIdx.x] = tc;
+        part[2 * (size_t)blockIdx.x + 1] = tb;
+    }
+}
+
+// one block: the nb block sums -> their exclusive prefixes, kSegBlock at a time with a carry;
+// the totals, and the total count as a u32 to `count` unless that is null
+__global__ __launch_bounds__(kSegBlock)
+void scan_parts_kernel(uint64_t* __restrict__ part, uint32_t nb, uint64_t* __restrict__ totals,
+                       uint32_t* __restrict__ count) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    uint64_t ca = 0, cb = 0;
+    for (uint32_t base = 0; base < nb; base += kSegBlock) {
+        const uint32_t k = base + threadIdx.x;
+        uint64_t a = k < nb ? part[2 * (size_t)k] : 0, b = k < nb ? part[2 * (size_t)k + 1] : 0;
+        uint64_t ta, tb;
+        block_excl_scan2(a, b, ta, tb, red);
+        if (k < nb) {
+            part[2 * (size_t)k] = ca + a;
+            part[2 * (size_t)k + 1] = cb + b;
+        }
+        ca += ta;
+        cb += tb;
+    }
+    if (threadIdx.x == 0) {
+        totals[0] = ca;
+        totals[1] = cb;
+        if (count) *count = (uint32_t)ca;
+    }
 }
 
 // bytes [lo, hi) of dword v to the output at x (4-B aligned): one dword store, or bytes

@@ -21,8 +21,9 @@
 //             loads and a byte funnel shift per chunk), sums the bytes it copies (absolute
 //             destination phase, be_sum), and then writes the header with the patched fields
 //             and the two checksums.  A pass-through frame is the same copy without the sum.
-// The copy, the header write, the record stage and the block scan are in rpkt_segcopy.h, which
-// rpkt_coalesce.hip (the inverse entry) shares.
+// What a record says about a TCP frame (tcp_where), the record stage, the block scan and the
+// kernel over the block sums, the copy, the header write, the entries' argument checks and the
+// workspace carving are in rpkt_segcopy.h, which rpkt_coalesce.hip (the inverse entry) shares.
 // Every load goes through the frames buffer resource and every store through one over
 // [out_frames_dev, + out_bytes); an overflowing batch (totals past the capacities) writes
 // its totals and seg_first and nothing else.
@@ -37,8 +38,6 @@
 // rpkt_gpu_parse_chains calls TCP: there a header may start where a segment ends but never
 // straddles an end), and byte by byte through the segment list otherwise, its sums then
 // taken at the logical position's parity.
-#include "rpkt_common.h"
-#include "rpkt_args.h"
 #include "rpkt_segcopy.h"
 
 namespace {
@@ -49,17 +48,15 @@ struct SegWs {
     u32x4*    plan;
     uint64_t* obase;
     uint64_t* part;
+    size_t    bytes;
 };
-inline uint32_t seg_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSegBlock - 1) / kSegBlock); }
-inline size_t seg_ws_bytes(uint32_t n) {
-    return (size_t)n * 32u + (((size_t)n * 8u + 15u) & ~(size_t)15u) + (size_t)seg_blocks(n) * 16u;
-}
 inline SegWs seg_ws(void* ws, uint32_t n) {
-    uint8_t* p = static_cast<uint8_t*>(ws);
+    Carve c(ws);
     SegWs w;
-    w.plan = reinterpret_cast<u32x4*>(p);
-    w.obase = reinterpret_cast<uint64_t*>(p + (size_t)n * 32u);
-    w.part = reinterpret_cast<uint64_t*>(p + (size_t)n * 32u + (((size_t)n * 8u + 15u) & ~(size_t)15u));
+    w.plan = c.take<u32x4>(2 * (size_t)n);
+    w.obase = c.take<uint64_t>(n);
+    w.part = c.take<uint64_t>(2 * (size_t)blocks(n));
+    w.bytes = c.used();
     return w;
 }
 
@@ -70,29 +67,6 @@ inline SegWs seg_ws(void* ws, uint32_t n) {
 constexpr uint32_t kSegOn = 1u, kSegV6 = 2u;
 
 // ---- 1. plan ---------------------------------------------------------------------------
-
-// What the staged record `w` says about a frame of `len` bytes at `mss`.
-struct SegWhat {
-    bool seg, v6;
-    uint32_t l3, l4, po, pl, pdst;
-};
-__device__ __forceinline__ SegWhat seg_decide(const uint32_t* w, bool valid, uint32_t len,
-                                              uint32_t mss) {
-    const uint32_t w0 = w[0], w5 = w[5], w7 = w[7], w8 = w[8], w16 = w[16], w17 = w[17];
-    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
-    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
-    const bool v6 = det == 0x86ddu;
-    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
-    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
-    // offsets that nest as a parse of this frame leaves them; [po, + pl) inside the frame
-    const bool nest = l4 >= l3 && po >= l4 && po <= len && po - l4 >= 20u && po - l4 <= 60u &&
-                      (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
-    uint32_t pl = w17 >> 16;
-    if (nest && pl > len - po) pl = len - po;
-    const bool seg = valid && status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
-                     (v6 || (frag & 0x3fffu) == 0u) && nest && pl > mss;
-    return SegWhat{seg, v6, l3, l4, po, pl, pdst};
-}
 
 // The header bytes of a flat frame at `off` of the frames buffer: dw(x), header bytes
 // x .. x + 3 as a little-endian dword; sum(a, b), the big-endian RFC 1071 sum of [a, b).
@@ -108,7 +82,7 @@ struct FlatHeader {
 // Plan words 2..7 of a segmented frame from its header H: the constants all its segments
 // share.
 template <class Header>
-__device__ __forceinline__ void seg_constants(const Header& H, const SegWhat& s, uint32_t (&p)[8]) {
+__device__ __forceinline__ void seg_constants(const Header& H, const TcpWhere& s, uint32_t (&p)[8]) {
     const uint32_t l3 = s.l3, l4 = s.l4, po = s.po;
     // a field leaves a sum by adding its complement (one's complement arithmetic;
     // the sums stay positive, so the folded values are the plain sums')
@@ -121,8 +95,7 @@ __device__ __forceinline__ void seg_constants(const Header& H, const SegWhat& s,
         ipc = H.sum(l3, l4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ ident) + (0xffffu ^ be16_hi(ip2));
         pseudo = H.sum(l3 + 12u, l3 + 20u);
     } else {
-        // the pseudo destination: rpkt_gpu_build_batch's rule
-        const uint32_t pd = (s.pdst >= l3 + 24u && s.pdst + 16u <= l4) ? s.pdst : l3 + 24u;
+        const uint32_t pd = ip6_pseudo_dst(s.pdst, l3, l4);
         pseudo = H.sum(l3 + 8u, l3 + 24u) + H.sum(pd, pd + 16u);
     }
     const uint32_t t1 = H.dw(l4 + 4u), t3 = H.dw(l4 + 12u);
@@ -150,12 +123,7 @@ __device__ __forceinline__ void plan_store(bool valid, uint32_t i, const uint32_
         seg_first[i] = (uint32_t)cnt;
         obase[i] = bytes;
     }
-    uint64_t tc, tb;
-    block_excl_scan2(cnt, bytes, tc, tb, red);
-    if (threadIdx.x == 0) {
-        part[2 * (size_t)blockIdx.x] = tc;
-        part[2 * (size_t)blockIdx.x + 1] = tb;
-    }
+    block_sums_to_part(cnt, bytes, part, red);
 }
 
 __global__ __launch_bounds__(kSegBlock)
@@ -178,14 +146,14 @@ void segment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         uint32_t* st = stage[wave];
         stage_records_tile(st, recs, p0, n, lane);
         const Frame fr = valid ? frame_span(offsets, stride, frame_len, fb, i) : Frame{0u, 0u};
-        const SegWhat s = seg_decide(st + lane * 21, valid, fr.len, mss);
+        const TcpWhere s = tcp_where(st + lane * 21, fr.len);
         p[0] = fr.off;
         p[1] = fr.len;
         if (valid) {
             cnt = 1;
             bytes = fr.len;
         }
-        if (s.seg) {
+        if (valid && s.tcp && s.pl > mss) {                       // segmented
             cnt = (s.pl + mss - 1u) / mss;
             bytes = cnt * s.po + s.pl;
             seg_constants(FlatHeader{make_rsrc(frames, fb), fb, fr.off}, s, p);
@@ -288,14 +256,14 @@ void segment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
         // a chain of 4 GiB or more cannot fit out_bytes: the call overflows and the write
         // never sees this plan; the record's offsets are 16 bits wide, so saturating is exact
         const uint32_t len = pkt < 0xffffffffull ? (uint32_t)pkt : 0xffffffffu;
-        const SegWhat s = seg_decide(st + lane * 21, valid, len, mss);
+        const TcpWhere s = tcp_where(st + lane * 21, len);
         p[0] = a;
         p[1] = len;
         if (valid) {
             cnt = 1;
             bytes = pkt;
         }
-        if (s.seg) {
+        if (valid && s.tcp && s.pl > mss) {                       // segmented
             cnt = (s.pl + mss - 1u) / mss;
             bytes = cnt * s.po + s.pl;
             const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
@@ -310,32 +278,7 @@ void segment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
 
 // ---- 2. scan ---------------------------------------------------------------------------
 
-// one block: the block sums -> their exclusive prefixes, kSegBlock at a time with a carry;
-// the totals
-__global__ __launch_bounds__(kSegBlock)
-void segment_scan_parts_kernel(uint64_t* __restrict__ part, uint32_t nb, uint32_t n,
-                               uint32_t* __restrict__ seg_first, uint64_t* __restrict__ totals) {
-    __shared__ uint64_t red[2 * kWavesPerBlock];
-    uint64_t ca = 0, cb = 0;
-    for (uint32_t base = 0; base < nb; base += kSegBlock) {
-        const uint32_t k = base + threadIdx.x;
-        uint64_t a = k < nb ? part[2 * (size_t)k] : 0, b = k < nb ? part[2 * (size_t)k + 1] : 0;
-        uint64_t ta, tb;
-        block_excl_scan2(a, b, ta, tb, red);
-        if (k < nb) {
-            part[2 * (size_t)k] = ca + a;
-            part[2 * (size_t)k + 1] = cb + b;
-        }
-        ca += ta;
-        cb += tb;
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = ca;
-        totals[1] = cb;
-        seg_first[n] = (uint32_t)ca;
-    }
-}
-
+// after scan_parts_kernel (rpkt_segcopy.h) over the block sums, which also stores seg_first[n]:
 // one block per kSegBlock frames: counts and bytes -> seg_first and the output byte bases
 __global__ __launch_bounds__(kSegBlock)
 void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
@@ -622,9 +565,9 @@ void segment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
 template <typename... KArgs, typename... Args>
 int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, uint32_t out_cap,
                    uint32_t* seg_first_dev, uint64_t* totals_dev, hipStream_t st, Args... args) {
-    const uint32_t nb = seg_blocks(n);
-    RPKT_TRY(launch(segment_scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, n,
-                    seg_first_dev, totals_dev));
+    const uint32_t nb = blocks(n);
+    RPKT_TRY(launch(scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, totals_dev,
+                    seg_first_dev + n));
     RPKT_TRY(launch(segment_scan_frames_kernel, dim3(nb), dim3(kSegBlock), 0, st, n, ws.part,
                     seg_first_dev, ws.obase));
     const uint64_t per_block = (uint64_t)kWavesPerBlock * kSegRun;        // outputs a block
@@ -636,26 +579,15 @@ int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, 
 
 extern "C" {
 
-size_t rpkt_gpu_segment_workspace_bytes(uint32_t n) { return seg_ws_bytes(n); }
+size_t rpkt_gpu_segment_workspace_bytes(uint32_t n) { return seg_ws(nullptr, n).bytes; }
 
 int rpkt_gpu_segment_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev, uint32_t mss,
                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                            uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                            uint64_t* totals_dev, void* workspace_dev, void* stream) {
-    if (!b || any_null(recs_dev, out_frames_dev, out_offsets_dev, seg_first_dev, totals_dev) ||
-        !workspace_dev)
-        return RPKT_E_INVAL;
-    RPKT_TRY(flags_ok(flags, 0u));
-    if (mss == 0u || mss > 65535u) return RPKT_E_INVAL;
+    RPKT_TRY(reframe_args_ok(b, recs_dev, mss, flags, 0u, out_frames_dev, out_bytes, out_offsets_dev,
+                             out_cap, seg_first_dev, totals_dev, workspace_dev));
     if (b->n == 0) return RPKT_OK;
-    RPKT_TRY(frames_ok(*b));
-    RPKT_TRY(size_ok(b->frames_bytes));
-    RPKT_TRY(size_ok(out_bytes));
-    RPKT_TRY(layout_ok(*b));
-    if (out_cap == 0u) return RPKT_E_INVAL;
-    if (misaligned(15, recs_dev, out_frames_dev) || misaligned(15, (const uint8_t*)workspace_dev) ||
-        misaligned(7, totals_dev))
-        return RPKT_E_ALIGN;
 
     const SegWs ws = seg_ws(workspace_dev, b->n);
     RPKT_TRY(launch_batch(segment_plan_kernel, kSegBlock, 0, stream, *b, recs_dev, mss, ws.plan,
@@ -666,29 +598,20 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev, ui
                           (uint32_t)out_bytes, out_offsets_dev, out_cap);
 }
 
-size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n_chains) { return seg_ws_bytes(n_chains); }
+size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n) { return seg_ws(nullptr, n).bytes; }
 
 int rpkt_gpu_segment_chains(const rpkt_chains_t* c, const rpkt_rec_t* recs_dev, uint32_t mss,
                             uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                             uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                             uint64_t* totals_dev, void* workspace_dev, void* stream) {
-    if (!c || any_null(recs_dev, out_frames_dev, out_offsets_dev, seg_first_dev, totals_dev) ||
-        !workspace_dev)
-        return RPKT_E_INVAL;
-    RPKT_TRY(flags_ok(flags, 0u));
-    if (mss == 0u || mss > 65535u) return RPKT_E_INVAL;
+    RPKT_TRY(reframe_args_ok(c, recs_dev, mss, flags, 0u, out_frames_dev, out_bytes, out_offsets_dev,
+                             out_cap, seg_first_dev, totals_dev, workspace_dev));
     if (c->n_chains == 0) return RPKT_OK;
-    RPKT_TRY(chains_ok(*c));
-    RPKT_TRY(size_ok(out_bytes));
-    if (out_cap == 0u) return RPKT_E_INVAL;
-    if (misaligned(7, c->segs_dev, totals_dev) || misaligned(15, recs_dev, out_frames_dev) ||
-        misaligned(15, (const uint8_t*)workspace_dev))
-        return RPKT_E_ALIGN;
 
     const uint32_t n = c->n_chains, fb = (uint32_t)c->buf_bytes;
     const uint32_t* segs = c->segs_dev;
     const SegWs ws = seg_ws(workspace_dev, n);
-    RPKT_TRY(launch(segment_chains_plan_kernel, dim3(seg_blocks(n)), dim3(kSegBlock), 0,
+    RPKT_TRY(launch(segment_chains_plan_kernel, dim3(blocks(n)), dim3(kSegBlock), 0,
                     (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, c->chain_first_dev, n,
                     recs_dev, mss, ws.plan, seg_first_dev, ws.obase, ws.part));
     return scan_and_write(segment_chains_write_kernel, ws, n, out_cap, seg_first_dev, totals_dev,

@@ -588,35 +588,52 @@ def forward_batch(batch, dmac, smac, forbid=None, keep=None, stream=None, flags=
     return keep
 
 
+def _workspace(name, n, device):
+    """The workspace tensor of a re-framing entry for n inputs (rpkt_gpu_<name>_workspace_bytes)."""
+    return _bytes(max(int(getattr(lib(), "rpkt_gpu_%s_workspace_bytes" % name)(n)), 16), 1, device)
+
+
 def segment_workspace(n, device="cuda"):
     """The workspace tensor of segment_batch for n input frames
     (rpkt_gpu_segment_workspace_bytes)."""
-    return _bytes(max(int(lib().rpkt_gpu_segment_workspace_bytes(n)), 16), 1, device)
+    return _workspace("segment", n, device)
 
 
-def _segment(name, src, what, recs, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
-             totals, workspace, stream, header_max):
-    """segment_batch and segment_chains: `src` (a DeviceBatch or DeviceChains) cut at `mss`
-    into a packed DeviceBatch; the default sizes from the documented bound over src's bytes."""
+def _reframe_outputs(what, src, recs, cap_bound, bytes_bound, out_frames, out_offsets, out_cap,
+                     out_bytes, first, first_name, totals, workspace, ws_name):
+    """The output side of the re-framing call `what` on `src`: out_cap and out_bytes from the
+    tensors given, else from the documented bounds cap_bound() and bytes_bound(out_cap); the
+    tensors not given (`first`: the n + 1 indices); RpktError for ones that do not fit."""
     torch = _torch()
-    dev = src.frames.device
-    n, fbytes = src.n, src.frames.numel()
+    dev, n = src.frames.device, src.n
     if out_cap is None:
-        out_cap = out_offsets.numel() - 1 if out_offsets is not None else n + fbytes // mss
+        out_cap = out_offsets.numel() - 1 if out_offsets is not None else cap_bound()
     if out_bytes is None:
-        out_bytes = out_frames.numel() if out_frames is not None else \
-            fbytes + (out_cap - n) * (134 if header_max is None else header_max)
+        out_bytes = out_frames.numel() if out_frames is not None else bytes_bound(out_cap)
     if out_frames is None:
         out_frames = _bytes(max(out_bytes, 16), 1, dev)
     if out_offsets is None:
         out_offsets = torch.empty(out_cap + 1, dtype=torch.int32, device=dev)
     if out_frames.numel() < out_bytes or out_offsets.numel() < out_cap + 1:
         raise RpktError("%s: outputs smaller than out_bytes / out_cap + 1" % what)
-    seg_first = torch.empty(n + 1, dtype=torch.int32, device=dev) if seg_first is None else seg_first
+    first = torch.empty(n + 1, dtype=torch.int32, device=dev) if first is None else first
     totals = torch.empty(2, dtype=torch.int64, device=dev) if totals is None else totals
-    workspace = segment_workspace(n, dev) if workspace is None else workspace
-    if recs.numel() != n * REC_BYTES or seg_first.numel() < n + 1:
-        raise RpktError("%s: records or seg_first do not fit %d frames" % (what, n))
+    workspace = _workspace(ws_name, n, dev) if workspace is None else workspace
+    if recs.numel() != n * REC_BYTES or first.numel() < n + 1:
+        raise RpktError("%s: records or %s do not fit %d frames" % (what, first_name, n))
+    return out_frames, out_bytes, out_offsets, out_cap, first, totals, workspace
+
+
+def _segment(name, src, what, recs, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
+             totals, workspace, stream, header_max):
+    """segment_batch and segment_chains: `src` (a DeviceBatch or DeviceChains) cut at `mss`
+    into a packed DeviceBatch; the default sizes from the documented bound over src's bytes."""
+    n, fbytes = src.n, src.frames.numel()
+    out_frames, out_bytes, out_offsets, out_cap, seg_first, totals, workspace = _reframe_outputs(
+        what, src, recs, lambda: n + fbytes // mss,
+        lambda cap: fbytes + (cap - n) * (134 if header_max is None else header_max),
+        out_frames, out_offsets, out_cap, out_bytes, seg_first, "seg_first", totals, workspace,
+        "segment")
     _call(name, ctypes.byref(src.desc()), recs.data_ptr(), mss, 0, out_frames.data_ptr(), out_bytes,
           out_offsets.data_ptr(), out_cap, seg_first.data_ptr(), totals.data_ptr(),
           workspace.data_ptr(), _stream_ptr(stream))
@@ -643,7 +660,7 @@ def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=N
 def segment_chains_workspace(n, device="cuda"):
     """The workspace tensor of segment_chains for n chains
     (rpkt_gpu_segment_chains_workspace_bytes)."""
-    return _bytes(max(int(lib().rpkt_gpu_segment_chains_workspace_bytes(n)), 16), 1, device)
+    return _workspace("segment_chains", n, device)
 
 
 def segment_chains(chains, recs, mss, out_frames=None, out_offsets=None, out_cap=None,
@@ -667,7 +684,7 @@ COALESCE_TRUST_SUMS = 1
 def coalesce_workspace(n, device="cuda"):
     """The workspace tensor of coalesce_batch for n positions
     (rpkt_gpu_coalesce_workspace_bytes)."""
-    return _bytes(max(int(lib().rpkt_gpu_coalesce_workspace_bytes(n)), 16), 1, device)
+    return _workspace("coalesce", n, device)
 
 
 def coalesce_batch(batch, recs, order=None, max_payload=65535, trust_sums=False, out_frames=None,
@@ -684,24 +701,11 @@ def coalesce_batch(batch, recs, order=None, max_payload=65535, trust_sums=False,
     batch overflowed and `out` is unspecified.  By default the outputs are sized from the
     documented bound: out_cap = n slots and out_bytes = frames_bytes (without an order; with one
     give out_bytes when it repeats frames)."""
-    torch = _torch()
-    dev = batch.frames.device
-    n, fbytes = batch.n, batch.frames.numel()
-    if out_cap is None:
-        out_cap = out_offsets.numel() - 1 if out_offsets is not None else max(n, 1)
-    if out_bytes is None:
-        out_bytes = out_frames.numel() if out_frames is not None else fbytes
-    if out_frames is None:
-        out_frames = _bytes(max(out_bytes, 16), 1, dev)
-    if out_offsets is None:
-        out_offsets = torch.empty(out_cap + 1, dtype=torch.int32, device=dev)
-    if out_frames.numel() < out_bytes or out_offsets.numel() < out_cap + 1:
-        raise RpktError("coalesce_batch: outputs smaller than out_bytes / out_cap + 1")
-    src_first = torch.empty(n + 1, dtype=torch.int32, device=dev) if src_first is None else src_first
-    totals = torch.empty(2, dtype=torch.int64, device=dev) if totals is None else totals
-    workspace = coalesce_workspace(n, dev) if workspace is None else workspace
-    if recs.numel() != n * REC_BYTES or src_first.numel() < n + 1:
-        raise RpktError("coalesce_batch: records or src_first do not fit %d frames" % n)
+    n = batch.n
+    out_frames, out_bytes, out_offsets, out_cap, src_first, totals, workspace = _reframe_outputs(
+        "coalesce_batch", batch, recs, lambda: max(n, 1), lambda cap: batch.frames.numel(),
+        out_frames, out_offsets, out_cap, out_bytes, src_first, "src_first", totals, workspace,
+        "coalesce")
     if order is not None and (order.numel() < n or order.element_size() != 4):
         raise RpktError("coalesce_batch: order takes %d 32-bit entries" % n)
     if out_mss is not None and (out_mss.numel() < n or out_mss.element_size() != 2):

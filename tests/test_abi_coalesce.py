@@ -38,6 +38,18 @@ def call(fn, b, max_payload=65535, flags=0, out_bytes=1 << 16, out_cap=64, **ptr
               p["totals"], p["workspace"], None)
 
 
+def test_the_workspace_sizes_are_pinned(fn):
+    """rpkt_gpu_segment_workspace_bytes and rpkt_gpu_coalesce_workspace_bytes: the values of
+    the layouts written out by hand (32 B of plan and a u64 per input, coalescing's u32 per
+    input, 16 B and coalescing's u32 per block of 256; each region a multiple of 16 B)."""
+    L = engine.lib()
+    want = {0: (0, 0), 1: (64, 96), 255: (10224, 11264), 256: (10256, 11296), 257: (10320, 11376),
+            70000: (2804384, 3085488)}
+    for n, (seg, co) in want.items():
+        assert L.rpkt_gpu_segment_workspace_bytes(n) == seg and seg % 16 == 0, n
+        assert L.rpkt_gpu_coalesce_workspace_bytes(n) == co and co % 16 == 0, n
+
+
 def test_argument_checks_in_the_documented_order(fn):
     """One case per check; each also breaks a later check, which must not be the one
     reported."""

@@ -11,10 +11,10 @@ from rpkt_amd import engine, gen, graphs
 from rpkt_amd.records import F_FLOW_EV, as_records
 
 import coalesce_model as cm
+import reframe_check as rc
 import segment_model as sm
 
 pytestmark = pytest.mark.gpu
-GUARD = 256                                    # elements after each output buffer
 
 
 @pytest.fixture(scope="module")
@@ -24,38 +24,9 @@ def torch():
     return t
 
 
-class Outputs:
-    """The entry's outputs on the device, 0xa5-filled, each with GUARD elements after it."""
-
-    def __init__(self, torch, n, out_cap, out_bytes):
-        def filled(count, dtype):
-            t = torch.empty(count + GUARD, dtype=dtype, device="cuda")
-            t.view(torch.uint8).fill_(0xa5)
-            return t
-        self.n, self.out_cap, self.out_bytes = n, out_cap, out_bytes
-        self.frames = filled((out_bytes + 15) // 16 * 16, torch.uint8)
-        self.offsets = filled(out_cap + 1, torch.int32)
-        self.src_first = filled(n + 1, torch.int32)
-        self.out_mss = filled(n, torch.int16)
-        self.totals = filled(2, torch.int64)
-        self.ws = engine.coalesce_workspace(n)
-
-    def call(self, db, recs, order=None, max_payload=65535, trust_sums=False):
-        return engine.coalesce_batch(db, recs, order, max_payload, trust_sums, out_frames=self.frames,
-                                     out_offsets=self.offsets, out_cap=self.out_cap,
-                                     out_bytes=self.out_bytes, src_first=self.src_first,
-                                     out_mss=self.out_mss, totals=self.totals, workspace=self.ws)
-
-    def host(self):
-        u8 = lambda t: t.cpu().numpy().view(np.uint8)                       # noqa: E731
-        return (u8(self.frames), self.offsets.cpu().numpy().view(np.uint32),
-                self.src_first.cpu().numpy().view(np.uint32),
-                self.out_mss.cpu().numpy().view(np.uint16),
-                self.totals.cpu().numpy().view(np.uint64))
-
-
-def first_diff(a, b):
-    return int(np.nonzero(a != b)[0][0])
+def Outputs(torch, n, out_cap, out_bytes):
+    return rc.Outputs(torch, n, out_cap, out_bytes, engine.coalesce_batch, engine.coalesce_workspace(n),
+                      "src_first", (("out_mss", n, torch.int16),))
 
 
 def check_case(torch, hb, order=None, max_payload=65535, trust_sums=False, out_cap=None,
@@ -68,9 +39,8 @@ def check_case(torch, hb, order=None, max_payload=65535, trust_sums=False, out_c
     out, first, totals, mss = want
     n = hb.n
     assert order is None or len(order) == n
-    n_out, need = int(totals[0]), int(totals[1])
-    out_cap = n_out + 5 if out_cap is None else out_cap
-    out_bytes = need + 7 if out_bytes is None else out_bytes
+    out_cap = int(totals[0]) + 5 if out_cap is None else out_cap
+    out_bytes = int(totals[1]) + 7 if out_bytes is None else out_bytes
     db = engine.DeviceBatch.from_host(hb)
     recs = engine.parse_batch(db, sm.F6)
     dorder = None
@@ -83,31 +53,11 @@ def check_case(torch, hb, order=None, max_payload=65535, trust_sums=False, out_c
     torch.cuda.synchronize()
     assert torch.equal(db.frames, f0) and torch.equal(recs, r0), "%s: the inputs were written" % what
     assert o0 is None or torch.equal(dorder, o0), "%s: the order was written" % what
-    gf, go, gs, gm, gt = o.host()
-    # src_first, out_mss and totals are exact whatever the capacities; the guards are intact
-    assert list(gt[:2]) == [n_out, need], "%s: totals %s, want %s" % (what, gt[:2], (n_out, need))
-    assert np.array_equal(gs[:n + 1], first), "%s: src_first at %d" % (what, first_diff(gs[:n + 1], first))
-    assert np.array_equal(gm[:n], mss), "%s: out_mss at %d" % (what, first_diff(gm[:n], mss))
-    assert (gs[n + 1:] == 0xa5a5a5a5).all() and (gt[2:] == 0xa5a5a5a5a5a5a5a5).all(), what
+    # out_mss, as src_first and totals, is exact whatever the capacities; its guard is intact
+    gm = o.host()[3]
+    assert np.array_equal(gm[:n], mss), "%s: out_mss at %d" % (what, rc.first_diff(gm[:n], mss))
     assert (gm[n:] == 0xa5a5).all(), what
-    assert (gf[out_bytes:] == 0xa5).all(), "%s: bytes past out_bytes written" % what
-    assert (go[out_cap + 1:] == 0xa5a5a5a5).all(), "%s: offsets past out_cap written" % what
-    if n_out > out_cap or need > out_bytes:
-        return want                                                 # overflow: the rest is unspecified
-    blob, offs = sm.packed_output(out, out_cap)
-    assert np.array_equal(go[:out_cap + 1], offs), "%s: out_offsets at %d" % (
-        what, first_diff(go[:out_cap + 1], offs))
-    if not np.array_equal(gf[:need], blob):
-        at = first_diff(gf[:need], blob)
-        j = int(np.searchsorted(offs, at, side="right")) - 1
-        raise AssertionError("%s: output byte %d differs (output frame %d, its byte %d): gpu %#x want %#x"
-                             % (what, at, j, at - int(offs[j]), gf[at], blob[at]))
-    assert (gf[need:out_bytes] == 0xa5).all(), "%s: bytes past out_bytes_needed written" % what
-    if parse_back:
-        # the GPU's parse over all out_cap slots of the GPU's output: the oracle's of the model's
-        g = as_records(engine.parse_batch(odb, sm.F6).cpu().numpy())
-        w = oracle.parse_batch(blob, out_cap, sm.F6, offsets=offs)
-        assert g.tobytes() == w.tobytes(), "%s: the parse of the output differs" % what
+    rc.check_outputs(o, odb, out, first, totals, what, parse_back)
     return want
 
 

@@ -9,10 +9,10 @@ from oracle import oracle
 from rpkt_amd import engine, gen, graphs
 from rpkt_amd.records import as_records
 
+import reframe_check as rc
 import segment_model as sm
 
 pytestmark = pytest.mark.gpu
-GUARD = 256                                    # elements after each output buffer
 
 
 @pytest.fixture(scope="module")
@@ -22,35 +22,9 @@ def torch():
     return t
 
 
-class Outputs:
-    """The entry's outputs on the device, 0xa5-filled, each with GUARD elements after it."""
-
-    def __init__(self, torch, n, out_cap, out_bytes):
-        def filled(count, dtype):
-            t = torch.empty(count + GUARD, dtype=dtype, device="cuda")
-            t.view(torch.uint8).fill_(0xa5)
-            return t
-        self.n, self.out_cap, self.out_bytes = n, out_cap, out_bytes
-        self.frames = filled((out_bytes + 15) // 16 * 16, torch.uint8)
-        self.offsets = filled(out_cap + 1, torch.int32)
-        self.seg_first = filled(n + 1, torch.int32)
-        self.totals = filled(2, torch.int64)
-        self.ws = engine.segment_workspace(n)
-
-    def call(self, db, recs, mss):
-        return engine.segment_batch(db, recs, mss, out_frames=self.frames, out_offsets=self.offsets,
-                                    out_cap=self.out_cap, out_bytes=self.out_bytes,
-                                    seg_first=self.seg_first, totals=self.totals, workspace=self.ws)
-
-    def host(self):
-        u8 = lambda t: t.cpu().numpy().view(np.uint8)                       # noqa: E731
-        return (u8(self.frames), self.offsets.cpu().numpy().view(np.uint32),
-                self.seg_first.cpu().numpy().view(np.uint32),
-                self.totals.cpu().numpy().view(np.uint64))
-
-
-def first_diff(a, b):
-    return int(np.nonzero(a != b)[0][0])
+def Outputs(torch, n, out_cap, out_bytes):
+    return rc.Outputs(torch, n, out_cap, out_bytes, engine.segment_batch, engine.segment_workspace(n),
+                      "seg_first")
 
 
 def check_case(torch, hb, mss, out_cap=None, out_bytes=None, what="", parse_back=True, want=None):
@@ -58,9 +32,8 @@ def check_case(torch, hb, mss, out_cap=None, out_bytes=None, what="", parse_back
     than the model's totals (spare slots and spare bytes to check); smaller ones overflow.
     Returns the model's (out_frames, seg_first, totals)."""
     out, first, totals = want if want is not None else sm.segment(hb, sm.oracle_records(hb), mss)
-    n_out, need = int(totals[0]), int(totals[1])
-    out_cap = n_out + 5 if out_cap is None else out_cap
-    out_bytes = need + 7 if out_bytes is None else out_bytes
+    out_cap = int(totals[0]) + 5 if out_cap is None else out_cap
+    out_bytes = int(totals[1]) + 7 if out_bytes is None else out_bytes
     db = engine.DeviceBatch.from_host(hb)
     recs = engine.parse_batch(db, sm.F6)
     f0, r0 = db.frames.clone(), recs.clone()
@@ -68,29 +41,7 @@ def check_case(torch, hb, mss, out_cap=None, out_bytes=None, what="", parse_back
     odb, _, _ = o.call(db, recs, mss)
     torch.cuda.synchronize()
     assert torch.equal(db.frames, f0) and torch.equal(recs, r0), "%s: the inputs were written" % what
-    gf, go, gs, gt = o.host()
-    # seg_first and totals are exact whatever the capacities; the guards are intact
-    assert np.array_equal(gs[:hb.n + 1], first), "%s: seg_first at %d" % (what, first_diff(gs[:hb.n + 1], first))
-    assert list(gt[:2]) == [n_out, need], "%s: totals %s, want %s" % (what, gt[:2], (n_out, need))
-    assert (gs[hb.n + 1:] == 0xa5a5a5a5).all() and (gt[2:] == 0xa5a5a5a5a5a5a5a5).all(), what
-    assert (gf[out_bytes:] == 0xa5).all(), "%s: bytes past out_bytes written" % what
-    assert (go[out_cap + 1:] == 0xa5a5a5a5).all(), "%s: offsets past out_cap written" % what
-    if n_out > out_cap or need > out_bytes:
-        return out, first, totals                                   # overflow: the rest is unspecified
-    blob, offs = sm.packed_output(out, out_cap)
-    assert np.array_equal(go[:out_cap + 1], offs), "%s: out_offsets at %d" % (
-        what, first_diff(go[:out_cap + 1], offs))
-    if not np.array_equal(gf[:need], blob):
-        at = first_diff(gf[:need], blob)
-        j = int(np.searchsorted(offs, at, side="right")) - 1
-        raise AssertionError("%s: output byte %d differs (output frame %d, its byte %d): gpu %#x want %#x"
-                             % (what, at, j, at - int(offs[j]), gf[at], blob[at]))
-    assert (gf[need:out_bytes] == 0xa5).all(), "%s: bytes past out_bytes_needed written" % what
-    if parse_back:
-        # the GPU's parse over all out_cap slots of the GPU's output: the oracle's of the model's
-        g = as_records(engine.parse_batch(odb, sm.F6).cpu().numpy())
-        w = oracle.parse_batch(blob, out_cap, sm.F6, offsets=offs)
-        assert g.tobytes() == w.tobytes(), "%s: the parse of the output differs" % what
+    rc.check_outputs(o, odb, out, first, totals, what, parse_back)
     return out, first, totals
 
 

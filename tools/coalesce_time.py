@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from segment_time import HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, super_frames  # noqa: E402
+from segment_time import HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, super_frames, time_legs  # noqa: E402
 
 
 def main():
@@ -44,8 +44,6 @@ def main():
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace or counter pass")
     a = ap.parse_args()
-    import time
-
     import torch
     from rpkt_amd import engine
     from rpkt_amd.records import as_records
@@ -92,26 +90,7 @@ def main():
         torch.cuda.synchronize()
         return
     legs = {"coalesce_batch": coalesce, "device_copy": copy, "segment_batch": segment}
-    k, t_w = 0, time.perf_counter()
-    while k < 8 or time.perf_counter() - t_w < 0.3:
-        for fn in legs.values():
-            fn(k)
-        k += 1
-        if k % 8 == 0:
-            torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    ms = {name: [] for name in legs}
-    for r in range(a.rounds + 1):
-        for name, fn in legs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for j in range(a.launches):
-                fn(j)
-            e1.record(stream)
-            torch.cuda.synchronize()
-            if r:
-                ms[name].append(e0.elapsed_time(e1) / a.launches)
-    med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+    med, ms = time_legs(torch, stream, legs, a.launches, a.rounds)
 
     # the output is the source (checked on both batches)
     for k in range(R):

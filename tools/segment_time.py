@@ -93,6 +93,33 @@ def mbuf_chains(torch, engine, db, n, seed):
                                first.to(torch.int32), n)
 
 
+def time_legs(torch, stream, legs, launches, rounds):
+    """Time the functions of `legs` (name -> fn(k)) as the docstring above says: warm-up for at
+    least 0.3 s, then rounds + 1 interleaved rounds of `launches` calls between two events, the
+    first round thrown away.  Returns (median ms a call, every kept round's ms a call) by name."""
+    import time
+    k, t_w = 0, time.perf_counter()
+    while k < 8 or time.perf_counter() - t_w < 0.3:
+        for fn in legs.values():
+            fn(k)
+        k += 1
+        if k % 8 == 0:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for r in range(rounds + 1):
+        for name, fn in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for j in range(launches):
+                fn(j)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if r:
+                ms[name].append(e0.elapsed_time(e1) / launches)
+    return {name: sorted(v)[len(v) // 2] for name, v in ms.items()}, ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -105,8 +132,6 @@ def main():
                     help="no timing: this many calls, for a kernel-trace pass")
     a = ap.parse_args()
     a.out = a.out or ("profiles/segment_chains/times.json" if a.chains else "profiles/segment/times.json")
-    import time
-
     import torch
     from rpkt_amd import engine
     from rpkt_amd.records import as_records
@@ -157,26 +182,7 @@ def main():
             (segment_chains if a.chains else segment)(k)
         torch.cuda.synchronize()
         return
-    k, t_w = 0, time.perf_counter()
-    while k < 8 or time.perf_counter() - t_w < 0.3:
-        for fn in legs.values():
-            fn(k)
-        k += 1
-        if k % 8 == 0:
-            torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    ms = {name: [] for name in legs}
-    for r in range(a.rounds + 1):
-        for name, fn in legs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for j in range(a.launches):
-                fn(j)
-            e1.record(stream)
-            torch.cuda.synchronize()
-            if r:
-                ms[name].append(e0.elapsed_time(e1) / a.launches)
-    med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+    med, ms = time_legs(torch, stream, legs, a.launches, a.rounds)
 
     # the workload is what it claims (the last call ran on batch (launches - 1) % R)
     segment(0)
