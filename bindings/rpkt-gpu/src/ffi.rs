@@ -73,6 +73,10 @@ pub const RPKT_BUILD_IP_CSUM: u32 = 1;
 pub const RPKT_BUILD_L4_CSUM: u32 = 2;
 /// rpkt_gpu_coalesce_batch: do not require valid sums in the records
 pub const RPKT_COALESCE_TRUST_SUMS: u32 = 1;
+/// rpkt_gpu_coalesce_batch: also coalesce UDP datagrams
+pub const RPKT_COALESCE_UDP: u32 = 16;
+/// rpkt_gpu_segment_batch, rpkt_gpu_segment_chains: also segment UDP datagrams
+pub const RPKT_SEGMENT_UDP: u32 = 16;
 
 // enum rpkt_opt_stop / rpkt_layer_stop
 pub const RPKT_OPT_NONE: u8 = 0;

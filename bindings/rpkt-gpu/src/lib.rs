@@ -440,7 +440,19 @@ pub fn segment_workspace_bytes(n: u32) -> usize {
 pub unsafe fn segment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mss: u32,
                             out: &SegmentOut, workspace_dev: *mut core::ffi::c_void,
                             stream: *mut core::ffi::c_void) -> Result<(), Error> {
-    check(ffi::rpkt_gpu_segment_batch(batch, recs_dev, mss, 0, out.frames_dev, out.out_bytes,
+    segment_batch_flags(batch, recs_dev, mss, 0, out, workspace_dev, stream)
+}
+
+/// segment_batch with the entry's `flags`: 0, or `ffi::RPKT_SEGMENT_UDP` to cut UDP datagrams
+/// longer than `mss` too (UDP GSO).
+///
+/// # Safety
+/// As for `segment_batch`.
+pub unsafe fn segment_batch_flags(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mss: u32,
+                                  flags: u32, out: &SegmentOut,
+                                  workspace_dev: *mut core::ffi::c_void,
+                                  stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_segment_batch(batch, recs_dev, mss, flags, out.frames_dev, out.out_bytes,
                                       out.offsets_dev, out.out_cap, out.seg_first_dev,
                                       out.totals_dev, workspace_dev, stream))
 }
@@ -463,7 +475,19 @@ pub fn segment_chains_workspace_bytes(n_chains: u32) -> usize {
 pub unsafe fn segment_chains(chains: &ffi::rpkt_chains_t, recs_dev: *const Rec, mss: u32,
                              out: &SegmentOut, workspace_dev: *mut core::ffi::c_void,
                              stream: *mut core::ffi::c_void) -> Result<(), Error> {
-    check(ffi::rpkt_gpu_segment_chains(chains, recs_dev, mss, 0, out.frames_dev, out.out_bytes,
+    segment_chains_flags(chains, recs_dev, mss, 0, out, workspace_dev, stream)
+}
+
+/// segment_chains with the entry's `flags`: 0 or `ffi::RPKT_SEGMENT_UDP`, as for
+/// `segment_batch_flags`.
+///
+/// # Safety
+/// As for `segment_chains`.
+pub unsafe fn segment_chains_flags(chains: &ffi::rpkt_chains_t, recs_dev: *const Rec, mss: u32,
+                                   flags: u32, out: &SegmentOut,
+                                   workspace_dev: *mut core::ffi::c_void,
+                                   stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_segment_chains(chains, recs_dev, mss, flags, out.frames_dev, out.out_bytes,
                                        out.offsets_dev, out.out_cap, out.seg_first_dev,
                                        out.totals_dev, workspace_dev, stream))
 }
@@ -504,6 +528,18 @@ pub unsafe fn coalesce_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec,
                              out: &CoalesceOut, workspace_dev: *mut core::ffi::c_void,
                              stream: *mut core::ffi::c_void) -> Result<(), Error> {
     let flags = if trust_sums { ffi::RPKT_COALESCE_TRUST_SUMS } else { 0 };
+    coalesce_batch_flags(batch, recs_dev, order_dev, max_payload, flags, out, workspace_dev, stream)
+}
+
+/// coalesce_batch with the entry's `flags`: any of `ffi::RPKT_COALESCE_TRUST_SUMS` and
+/// `ffi::RPKT_COALESCE_UDP` (merge UDP datagrams too: UDP GRO).
+///
+/// # Safety
+/// As for `coalesce_batch`.
+pub unsafe fn coalesce_batch_flags(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec,
+                                   order_dev: *const u32, max_payload: u32, flags: u32,
+                                   out: &CoalesceOut, workspace_dev: *mut core::ffi::c_void,
+                                   stream: *mut core::ffi::c_void) -> Result<(), Error> {
     check(ffi::rpkt_gpu_coalesce_batch(batch, recs_dev, order_dev, max_payload, flags,
                                        out.frames_dev, out.out_bytes, out.offsets_dev, out.out_cap,
                                        out.src_first_dev, out.out_mss_dev, out.totals_dev,

@@ -102,19 +102,20 @@ enum rpkt_status {
  *     order with its batch entry's checks, all before the first launch;
  *   rpkt_gpu_segment_batch: the batch entries' order with its own arguments in their places:
  *     a NULL batch, recs_dev, output (out_frames_dev, out_offsets_dev, seg_first_dev,
- *     totals_dev) or workspace_dev (E_INVAL); flags other than 0, then mss outside 1..65535
- *     (E_INVAL); n == 0 (RPKT_OK); NULL frames_dev (E_INVAL); frames_bytes, then out_bytes at
+ *     totals_dev) or workspace_dev (E_INVAL); flags other than 0 or RPKT_SEGMENT_UDP, then mss
+ *     outside 1..65535 (E_INVAL); n == 0 (RPKT_OK); NULL frames_dev (E_INVAL); frames_bytes, then out_bytes at
  *     the same limit (E_TOO_LARGE); no layout (E_INVAL); out_cap == 0 (E_INVAL); alignment
  *     (E_ALIGN): recs_dev, out_frames_dev, workspace_dev 16 B, totals_dev 8 B;
  *   rpkt_gpu_segment_chains: rpkt_gpu_segment_batch's order with the chain entries' checks in
  *     the batch's place: a NULL chains, recs_dev, output or workspace_dev (E_INVAL); flags other
- *     than 0, then mss outside 1..65535 (E_INVAL); n_chains == 0 (RPKT_OK); NULL
+ *     than 0 or RPKT_SEGMENT_UDP, then mss outside 1..65535 (E_INVAL); n_chains == 0 (RPKT_OK); NULL
  *     chain_first_dev, or with n_segs > 0 NULL buf_dev / segs_dev (E_INVAL); buf_bytes and
  *     n_segs (E_TOO_LARGE); out_bytes (E_TOO_LARGE); out_cap == 0 (E_INVAL); alignment
  *     (E_ALIGN): segs_dev and totals_dev 8 B, recs_dev, out_frames_dev, workspace_dev 16 B;
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
- *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags other than
- *     RPKT_COALESCE_TRUST_SUMS, then max_payload outside 1..65535 in mss's place.
+ *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
+ *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
+ *     mss's place.
  * Where an entry leaves that order (kept as it is, callers may rely on it):
  *   rpkt_gpu_parse_tunnel_batch and each slot of rpkt_gpu_parse_tunnel_ring test the flow
  *     events first, before n == 0: an empty batch with RPKT_F_FLOW_EV and no event buffer is
@@ -705,7 +706,7 @@ typedef struct rpkt_fwd {
 int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uint8_t* keep_dev,
                            void* stream);
 
-/* ---- TCP segmentation (TSO) ---------------------------------------------------- */
+/* ---- TCP and UDP segmentation (TSO, UDP GSO) ------------------------------------ */
 
 /* The third TX offload of the reference's examples: rpkt-dpdk/examples/tso_tx.rs:128-134
  * sets TCP_SEG (1 << 50) next to the IP_CKSUM / TCP_CKSUM bits, l2_len / l3_len / l4_len and
@@ -719,7 +720,7 @@ int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uin
  * frames; the sum flags do not matter).  As for rpkt_gpu_options_batch the records only
  * locate things -- status, the dispatch ethertype, ip_protocol, ip_frag, l3_off, l4_off,
  * payload_off, payload_len, ip6_pdst_off -- and every header byte is taken from the frame.
- * mss: 1..65535.  flags: 0 (reserved for UDP segmentation).
+ * mss: 1..65535.  flags: 0, or RPKT_SEGMENT_UDP to segment UDP datagrams too (below).
  *
  * Frame i is segmented iff status == RPKT_S_OK, ip_protocol == 6, for IPv4
  * (ip_frag & 0x3fff) == 0 (not a fragment) and payload_len > mss; it yields
@@ -739,6 +740,21 @@ int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uin
  *           a TCP one, over the pseudo header (for IPv6 its destination is the address at
  *           ip6_pdst_off under rpkt_gpu_build_batch's rule), the header and the segment's
  *           payload; a result of 0 stays 0.
+ *
+ * With RPKT_SEGMENT_UDP, TCP frames are handled as above and UDP datagrams are cut under the
+ * Linux __udp_gso_segment rules (the UDP_SEGMENT socket option, DPDK's rte_gso UDP path): a
+ * frame is also segmented iff status == RPKT_S_OK, ip_protocol == 17, for IPv4
+ * (ip_frag & 0x3fff) == 0, payload_off - l4_off == 8 and payload_len > mss; it yields
+ * n_i = ceil(payload_len / mss) frames.  Segment k: the bytes, the IPv4 packet_len, ident + k
+ * and checksum, and the IPv6 payload_len exactly as for TCP;
+ *   UDP     length (bytes l4+4..5) = 8 + p_k; ports copied; the checksum (bytes l4+6..7)
+ *           filled as RPKT_BUILD_L4_CSUM fills a UDP one, over the pseudo header (protocol 17,
+ *           the UDP length; the IPv6 destination as for TCP), the 8-byte header and the
+ *           segment's payload; a result of 0 is written as 0xffff.  It is always filled, also
+ *           when the input's checksum field is 0: "no checksum" is not a property a cut can
+ *           carry (Linux refuses UDP_SEGMENT without a checksum).
+ * Without the flag a UDP frame passes through, as every output is then what it was before
+ * the flag existed.  One mss serves the call, TCP and UDP alike.
  *
  * Outputs:
  *   seg_first_dev  n + 1 entries: the outputs of frame i are [seg_first[i], seg_first[i+1]);
@@ -761,7 +777,12 @@ int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uin
  * unspecified, but every frame byte is read through the bounds-checked buffer resource with
  * [payload_off, + payload_len) clamped to the frame's span, and a record whose offsets do not
  * nest as a parse leaves them (l3_off + 20 (IPv6: 40) <= l4_off, l4_off + 20 <= payload_off
- * <= frame_len, header lengths within 60) passes through: wrong frames, never a fault. */
+ * <= frame_len, header lengths within 60; UDP: l4_off + 8 == payload_off) passes through:
+ * wrong frames, never a fault.
+ * Not covered: the inner TCP or UDP of tunnelled frames, a segment size per flow, IPv4 UDP
+ * fragmentation (UFO). */
+#define RPKT_SEGMENT_UDP  16u   /* also segment UDP datagrams (flags of both segment entries) */
+
 size_t rpkt_gpu_segment_workspace_bytes(uint32_t n);
 int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev, uint32_t mss,
                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
@@ -796,20 +817,21 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev
  *             and every store through one over the output: wrong records give wrong frames,
  *             never a fault.
  *   Limits    no cap on the segments of a chain (many tiny segments are slow, not wrong).
- * flags: 0 (reserved for UDP segmentation).  workspace_dev:
+ * flags: 0 or RPKT_SEGMENT_UDP, as for rpkt_gpu_segment_batch: a UDP header gathered across
+ * segment cuts is cut like a TCP one.  workspace_dev:
  * rpkt_gpu_segment_chains_workspace_bytes(n_chains) bytes, 16-byte aligned; calls that share
  * one must be ordered.  No host step: rpkt_gpu_parse_chains -> rpkt_gpu_segment_chains ->
  * rpkt_gpu_parse_batch over out_cap slots captures as one graph.
  * Bounds for sizing: rpkt_gpu_segment_batch's with the sum of the chains' pkt_len in
  * frames_bytes' place; that sum is at most buf_bytes when segments do not overlap.
- * Not covered: coalescing over chains, UDP, the inner TCP of tunnelled frames. */
+ * Not covered: coalescing over chains, the inner TCP or UDP of tunnelled frames. */
 size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n_chains);
 int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_dev, uint32_t mss,
                             uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                             uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                             uint64_t* totals_dev, void* workspace_dev, void* stream);
 
-/* ---- TCP receive coalescing (GRO / LRO) ------------------------------------------- */
+/* ---- TCP and UDP receive coalescing (GRO / LRO, UDP GRO) --------------------------- */
 
 /* The receive-side counterpart of rpkt_gpu_segment_batch: rpkt-dpdk/examples/lro_rx.rs turns
  * on the port's LRO offload (rx_offloads bit 4, with scatter) and reads each COALESCED TCP
@@ -827,8 +849,8 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_
  * order_dev (optional, n entries): position i holds frame order[i] (NULL: frame i), for
  * bursts whose flows interleave (a stable sort of the flow events' buckets).  An entry >= n
  * makes its position an empty frame: never read, a zero-length output.  It need not be a
- * permutation.  max_payload: 1..65535, the largest merged TCP payload.  flags: 0 or
- * RPKT_COALESCE_TRUST_SUMS.
+ * permutation.  max_payload: 1..65535, the largest merged payload.  flags: 0 or any of
+ * RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP (coalesce UDP datagrams too, below).
  *
  * A frame is ELIGIBLE iff status == RPKT_S_OK, ip_protocol == 6, for IPv4
  * (ip_frag & 0x3fff) == 0, payload_len >= 1, its offsets nest as segmentation requires, SYN
@@ -852,6 +874,20 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_
  * the group's payload stays <= min(max_payload, 65535 - ip_hdrs), ip_hdrs = payload_off -
  * l3_off (IPv4) or payload_off - l3_off - 40 (IPv6).
  *
+ * With RPKT_COALESCE_UDP, TCP frames are handled as above and UDP datagrams are merged under
+ * the Linux udp_gro_receive_segment rules (the UDP_GRO socket option, DPDK's rte_gro UDP
+ * path).  A UDP frame is ELIGIBLE iff status == RPKT_S_OK, ip_protocol == 17, it is no IPv4
+ * fragment, payload_len >= 1, its offsets nest with payload_off - l4_off == 8, its UDP checksum
+ * field is not 0 (also under TRUST_SUMS: a datagram sent without a checksum is never merged)
+ * and, without TRUST_SUMS, l4_sum == 0xffff and for IPv4 ip_sum == 0xffff.  B(i) for two UDP
+ * frames: both eligible, the same IP version, equal l3_off, l4_off and payload_off; header
+ * bytes [0, payload_off) equal, ignoring the IP bytes above and UDP bytes l4+4..7 (length,
+ * checksum); the IPv4 ident rule as for TCP; no sequence and no flag condition.  The protocol
+ * byte is compared, so a TCP frame never continues a UDP one.  short, link and the greedy cut
+ * are the same, so a run is datagrams of one size ending in at most one shorter one.  The
+ * rule is not Linux's sequential state machine here either, and Linux's cap of 64 datagrams
+ * per merge is not applied: min(max_payload, 65535 - ip_hdrs) is the only limit.
+ *
  * Outputs, in position order, one per group:
  *   a group of one frame   a byte copy of [0, frame_len), padding included;
  *   a merged group         the head's bytes [0, payload_off), then every member's
@@ -862,11 +898,14 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_
  *                          head's ORed with the last member's FIN and PSH; the TCP checksum
  *                          filled as segmentation fills it (the IPv6 pseudo destination from the
  *                          head's ip6_pdst_off under rpkt_gpu_build_batch's rule; 0 stays 0);
+ *                          for UDP the head's ports, UDP length = 8 + the total payload and the
+ *                          UDP checksum filled as segmentation fills it (0 written as 0xffff);
  *   src_first_dev  n + 1 entries: output j is made of positions [src_first[j],
  *                  src_first[j+1]); entries n_out+1..n equal n; exact whatever the capacities;
  *   out_mss_dev    optional, n entries: the head's payload_len for a merged output, 0 for a
  *                  copied one and for entries >= n_out -- the gso_size a later
- *                  rpkt_gpu_segment_batch needs; exact whatever the capacities;
+ *                  rpkt_gpu_segment_batch needs, and the one UDP_GRO hands the socket; exact
+ *                  whatever the capacities;
  *   totals_dev, out_frames_dev, out_offsets_dev, out_cap: rpkt_gpu_segment_batch's contract
  *                  exactly -- totals {n_out, out_bytes_needed} exact on overflow, spare offset
  *                  slots equal out_bytes_needed, nothing written outside the buffers.
@@ -876,8 +915,10 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_
  * parse -> coalesce captures as one graph.  Records from another batch give unspecified output
  * but never a fault: all loads go through the frames buffer resource and offsets that do not
  * nest make a frame ineligible.
- * Not covered: mbuf chains, the inner TCP of tunnelled frames, UDP. */
+ * Not covered: mbuf chains, the inner TCP or UDP of tunnelled frames, keeping an IPv4 "no
+ * checksum" across a merge. */
 #define RPKT_COALESCE_TRUST_SUMS 1u   /* do not require valid sums in the records */
+#define RPKT_COALESCE_UDP 16u   /* also coalesce UDP datagrams */
 
 size_t rpkt_gpu_coalesce_workspace_bytes(uint32_t n);
 int rpkt_gpu_coalesce_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev,

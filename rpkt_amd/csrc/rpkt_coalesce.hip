@@ -1,12 +1,15 @@
 // rpkt_coalesce.hip — rpkt_gpu_coalesce_batch: TCP receive coalescing (GRO / LRO) of a
 // device-resident batch, what the port's LRO offload does for rpkt-dpdk/examples/lro_rx.rs
-// and the inverse of rpkt_gpu_segment_batch (include/rpkt_gpu.h has the semantics).
+// and the inverse of rpkt_gpu_segment_batch (include/rpkt_gpu.h has the semantics).  With
+// RPKT_COALESCE_UDP also UDP datagrams (the Linux udp_gro_receive_segment rules): a second L4
+// rule in the plan's eligibility, the link's predicate and the header patches.
 //
 // Many input positions make one output, so the work is planned per position and the bytes
 // are placed by prefix sums.  Eight launches on the stream, no host step between them:
 //   1. plan    one lane per position: its frame (through order_dev), its record (coalesced
 //              through an LDS stage, or gathered under an order) and the three header dwords
-//              eligibility and the predicate need (ident / DF, seq, the flags);
+//              eligibility and the predicate need (ident / DF, seq, the flags; UDP: the
+//              checksum field);
 //   2. link    one lane per position: B(i), the masked compare of its header with its
 //              predecessor's, a dword of each per step through the buffer resource; B(i - 1)
 //              from the neighbouring lane (the block's first lane computes it); link and
@@ -29,7 +32,7 @@
 // its price is the second pass over the merged outputs' headers.  No kernel waits on
 // another workgroup and every loop is bounded by a count from the plan.
 // Shared with rpkt_segment.hip through rpkt_segcopy.h: which records are the TCP frames that
-// segmentation cuts (tcp_where), the record stage, the block scan and launch 5, the copy, the
+// segmentation cuts (l4_where), the record stage, the block scan and launch 5, the copy, the
 // header write, the entry's argument checks and the workspace carving.
 // Every load of frame bytes goes through the frames buffer resource and every store of
 // output bytes through one over [out_frames_dev, + out_bytes); an overflowing call (totals
@@ -62,10 +65,10 @@ inline CoWs co_ws(void* ws, uint32_t n) {
 }
 
 // plan words: 0 frame offset, 1 frame length, 2 l3 | l4 << 16, 3 payload_off | payload_len
-// << 16 (2 and 3: 0 unless eligible), 4 seq, 5 ident | TCP byte 13 << 16, 6 kCoElig | kCoV6 |
-// kCoDF | ip6_pdst_off << 16, 7 (from group on) kCoHead | kCoMerged | the run head's
-// payload_len << 16
-constexpr uint32_t kCoElig = 1u, kCoV6 = 2u, kCoDF = 4u;
+// << 16 (2 and 3: 0 unless eligible), 4 seq (UDP: 0), 5 ident | TCP byte 13 << 16 (UDP: 0),
+// 6 kCoElig | kCoV6 | kCoDF | kCoUdp | ip6_pdst_off << 16, 7 (from group on) kCoHead |
+// kCoMerged | the run head's payload_len << 16
+constexpr uint32_t kCoElig = 1u, kCoV6 = 2u, kCoDF = 4u, kCoUdp = 8u;
 constexpr uint32_t kCoHead = 1u, kCoMerged = 2u;
 // aux (link .. group): the block-local index + 1 of the position's run head (0: in an earlier
 // block) | kCoLink | kCoShort
@@ -75,6 +78,10 @@ constexpr uint32_t kFin = 0x01u, kSyn = 0x02u, kRst = 0x04u, kPsh = 0x08u, kUrg 
 
 // ---- 1. plan ---------------------------------------------------------------------------
 
+// <kUdp>: the entry's RPKT_COALESCE_UDP.  The kernels that test the protocol (plan, link,
+// header) take it as a template argument, so a call without the flag launches the code
+// without the tests.
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void coalesce_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
                           const uint32_t* __restrict__ offsets, uint32_t stride, uint32_t frame_len,
@@ -106,37 +113,41 @@ void coalesce_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
     const bool present = f < n;
     const Frame fr = present ? frame_span(offsets, stride, frame_len, fb, f) : Frame{0u, 0u};
     // the frames segmentation cuts, with a payload and sums that verified
-    const TcpWhere s = tcp_where(w0, w5, w7, w8, w16, w17, fr.len);
+    const L4Where s = l4_where(w0, w5, w7, w8, w16, w17, fr.len, kUdp);
     const bool v6 = s.v6;
     const uint32_t l3 = s.l3, l4 = s.l4, po = s.po, pl = s.pl, pdst = s.pdst;
     const bool sums = trust || ((w18 >> 16) == 0xffffu && (v6 || (w18 & 0xffffu) == 0xffffu));
-    bool elig = present && s.tcp && pl >= 1u && sums;
+    bool elig = present && s.on && pl >= 1u && sums;
     uint32_t seq = 0, idfl = 0, df = 0;
     if (elig) {
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
         const uint32_t a3 = fr.off + l3, a4 = fr.off + l4;
+        // t1: TCP's seq, UDP's length and checksum; a UDP frame has no byte 13 (t3 is payload)
         const uint32_t t1 = gdword(rs, fb, a4 + 4u), t3 = gdword(rs, fb, a4 + 12u);
-        const uint32_t tf = (t3 >> 8) & 0xffu;                    // TCP byte 13
-        seq = bswap32(t1);
+        const uint32_t tf = s.udp ? 0u : (t3 >> 8) & 0xffu;       // TCP byte 13
+        seq = s.udp ? 0u : bswap32(t1);
         idfl = tf << 16;
         if (!v6) {
             const uint32_t ip1 = gdword(rs, fb, a3 + 4u);
             idfl |= be16_lo(ip1);
             df = (be16_hi(ip1) & 0x4000u) ? kCoDF : 0u;
         }
-        elig = (tf & (kSyn | kRst | kUrg)) == 0u;
+        // a UDP datagram sent without a checksum (field 0) is not merged, sums trusted or not
+        elig = s.udp ? be16_hi(t1) != 0u : (tf & (kSyn | kRst | kUrg)) == 0u;
     }
     if (valid) {
         plan[2 * (size_t)i] = u32x4{fr.off, fr.len, elig ? l3 | (l4 << 16) : 0u,
                                     elig ? po | (pl << 16) : 0u};
-        plan[2 * (size_t)i + 1] = u32x4{seq, idfl, elig ? kCoElig | (v6 ? kCoV6 : 0u) | df | (pdst << 16) : 0u,
-                                        0u};
+        const uint32_t bits = kCoElig | (v6 ? kCoV6 : 0u) | df | (s.udp ? kCoUdp : 0u);
+        plan[2 * (size_t)i + 1] = u32x4{seq, idfl, elig ? bits | (pdst << 16) : 0u, 0u};
     }
 }
 
 // ---- 2. link ---------------------------------------------------------------------------
 
-// which bits of the header dword at frame offset x enter the compare
+// which bits of the header dword at frame offset x enter the compare.  One mask serves both
+// protocols: UDP's ignored bytes l4+4..7 (length, checksum) are where TCP's seq is, and its
+// header ends (po = l4 + 8) before the other TCP fields.
 __device__ __forceinline__ uint32_t header_keep(uint32_t x, uint32_t l3, uint32_t l4, uint32_t po,
                                                 bool v6) {
     uint32_t m = 0;
@@ -169,14 +180,17 @@ struct HeaderWalk {
 };
 
 // B(i), i >= 1: the frame at position i continues the one at i - 1
+template <bool kUdp>
 __device__ __forceinline__ bool base_pred(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
                                           const u32x4* __restrict__ plan, uint32_t i) {
     const u32x4 pa = plan[2 * (size_t)i], pb = plan[2 * (size_t)i + 1];
     const u32x4 qa = plan[2 * (size_t)i - 2], qb = plan[2 * (size_t)i - 1];
-    if (!(pb.z & qb.z & kCoElig) || ((pb.z ^ qb.z) & kCoV6)) return false;
+    if (!(pb.z & qb.z & kCoElig) || ((pb.z ^ qb.z) & (kCoV6 | (kUdp ? kCoUdp : 0u))))
+        return false;
     if (pa.z != qa.z || ((pa.w ^ qa.w) & 0xffffu)) return false;          // l3, l4, payload_off
     const bool v6 = (pb.z & kCoV6) != 0u;
-    if (pb.x != qb.x + (qa.w >> 16)) return false;                        // seq
+    // seq; UDP has no sequence and no flag condition (its flag words are 0)
+    if (!(kUdp && (pb.z & kCoUdp)) && pb.x != qb.x + (qa.w >> 16)) return false;
     if (!v6 && !(pb.z & kCoDF) && ((pb.y ^ (qb.y + 1u)) & 0xffffu)) return false;   // ident
     if (((qb.y >> 16) & (kFin | kPsh)) || ((pb.y >> 16) & kCwr)) return false;
     const uint32_t l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu;
@@ -199,6 +213,7 @@ __device__ __forceinline__ uint32_t block_incl_max(uint32_t v, uint32_t* red) {
     return x;
 }
 
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void coalesce_link_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
                           const u32x4* __restrict__ plan, uint32_t* __restrict__ aux,
@@ -208,12 +223,12 @@ void coalesce_link_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
     const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
     const bool valid = i < n;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
-    const bool bi = valid && i >= 1u && base_pred(rs, fb, plan, i);
+    const bool bi = valid && i >= 1u && base_pred<kUdp>(rs, fb, plan, i);
     bs[threadIdx.x] = bi ? 1u : 0u;
     __syncthreads();
     bool bp;                                                      // B(i - 1)
     if (threadIdx.x != 0u) bp = bs[threadIdx.x - 1u] != 0u;
-    else bp = valid && i >= 2u && base_pred(rs, fb, plan, i - 1u);
+    else bp = valid && i >= 2u && base_pred<kUdp>(rs, fb, plan, i - 1u);
     const uint32_t p = valid ? plan[2 * (size_t)i].w >> 16 : 0u;
     const uint32_t p1 = (valid && i >= 1u) ? plan[2 * (size_t)i - 2].w >> 16 : 0u;
     const uint32_t p2 = (valid && i >= 2u) ? plan[2 * (size_t)i - 4].w >> 16 : 0u;
@@ -386,6 +401,7 @@ void coalesce_copy_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
 #endif
 constexpr uint32_t kCoHdrRun = RPKT_CO_HDR_RUN;
 
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
                             const u32x4* __restrict__ plan, const uint64_t* __restrict__ obase,
@@ -409,24 +425,31 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
         const uint32_t d0 = (uint32_t)obase[i0];
         const uint32_t end = i1 < n ? (uint32_t)obase[i1] : (uint32_t)need;
         const uint32_t foff = pa.x, l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu;
-        const bool v6 = (pb.z & kCoV6) != 0u;
+        const bool v6 = (pb.z & kCoV6) != 0u, udp = kUdp && (pb.z & kCoUdp);   // wave-uniform
         const uint32_t pdst = pb.z >> 16;
         const uint32_t P = end - d0 - po;                                 // the merged payload
         // the members' payload sums, all at the absolute destination phase
         uint32_t s = 0;
         for (uint32_t m = i0 + (uint32_t)lane; m < i1; m += kWave) s += aux[m];   // <= 1024 each
         const uint32_t pay = be_sum(wave_sum(fold16(s)), d0 + po);
-        // the head's header sums, a lane each: IPv4 header, TCP header, pseudo addresses.  A
-        // field leaves a sum by adding its complement.
+        // the head's header sums, a lane each: IPv4 header, TCP (without flags and checksum) or
+        // UDP (without length and checksum) header, pseudo addresses.  A field leaves a sum by
+        // adding its complement.
         const uint32_t a3 = foff + l3, a4 = foff + l4;
         uint32_t x = 0, y = 0;
         if (lane == 0 && !v6) {
             const uint32_t ip0 = gdword(rs, fb, a3), ip2 = gdword(rs, fb, a3 + 8u);
             x = range_be_sum(rs, fb, a3, a4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ be16_hi(ip2));
         } else if (lane == 1) {
-            const uint32_t t3 = gdword(rs, fb, a4 + 12u), t4 = gdword(rs, fb, a4 + 16u);
-            y = be16_lo(t3);
-            x = range_be_sum(rs, fb, a4, foff + po) + (0xffffu ^ y) + (0xffffu ^ be16_lo(t4));
+            x = range_be_sum(rs, fb, a4, foff + po);
+            if (udp) {
+                const uint32_t t1 = gdword(rs, fb, a4 + 4u);
+                x += (0xffffu ^ be16_lo(t1)) + (0xffffu ^ be16_hi(t1));
+            } else {
+                const uint32_t t3 = gdword(rs, fb, a4 + 12u), t4 = gdword(rs, fb, a4 + 16u);
+                y = be16_lo(t3);
+                x += (0xffffu ^ y) + (0xffffu ^ be16_lo(t4));
+            }
         } else if (lane == 2) {
             if (!v6) {
                 x = range_be_sum(rs, fb, a3 + 12u, a3 + 20u);
@@ -437,7 +460,7 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
             }
         }
         const uint32_t ipc = (uint32_t)__builtin_amdgcn_readlane((int)x, 0);
-        const uint32_t tcpc = (uint32_t)__builtin_amdgcn_readlane((int)x, 1);
+        const uint32_t l4c = (uint32_t)__builtin_amdgcn_readlane((int)x, 1);
         const uint32_t pseudo = (uint32_t)__builtin_amdgcn_readlane((int)x, 2);
         uint32_t w12 = (uint32_t)__builtin_amdgcn_readlane((int)y, 1);
         w12 |= lastf & (kFin | kPsh);
@@ -452,10 +475,17 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
             Pt[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + P) & 0xffffu)};
             Pt[1] = SegPatch{0u, 0u, 0u};
         }
-        const uint32_t tlen = po - l4 + P;
-        const uint32_t tck = ~fold16(fold16(tcpc) + fold16(pseudo) + 6u + w12 + tlen + pay) & 0xffffu;
-        Pt[2] = SegPatch{l4 + 13u, 1u, w12 & 0xffu};
-        Pt[3] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
+        const uint32_t tlen = po - l4 + P;                                // UDP: 8 + P
+        if (udp) {
+            // the length is in the pseudo header and in the header; a result of 0 goes as 0xffff
+            const uint32_t uck = udp_csum_field(fold16(l4c) + fold16(pseudo) + 17u + 2u * tlen + pay);
+            Pt[2] = SegPatch{l4 + 4u, 4u, bswap16(tlen & 0xffffu) | (bswap16(uck) << 16)};
+            Pt[3] = SegPatch{0u, 0u, 0u};
+        } else {
+            const uint32_t tck = ~fold16(fold16(l4c) + fold16(pseudo) + 6u + w12 + tlen + pay) & 0xffffu;
+            Pt[2] = SegPatch{l4 + 13u, 1u, w12 & 0xffu};
+            Pt[3] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
+        }
         Pt[4] = SegPatch{0u, 0u, 0u};
         const uint32_t hfirst = header_dword(rs, fb, foff, d0, (uint32_t)lane);
         wave_copy_header(rs, fb, ro, foff, d0, po, hfirst, Pt, lane);
@@ -473,18 +503,19 @@ int rpkt_gpu_coalesce_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                             uint8_t* out_frames_dev, uint64_t out_bytes, uint32_t* out_offsets_dev,
                             uint32_t out_cap, uint32_t* src_first_dev, uint16_t* out_mss_dev,
                             uint64_t* totals_dev, void* workspace_dev, void* stream) {
-    RPKT_TRY(reframe_args_ok(b, recs_dev, max_payload, flags, RPKT_COALESCE_TRUST_SUMS, out_frames_dev,
-                             out_bytes, out_offsets_dev, out_cap, src_first_dev, totals_dev,
-                             workspace_dev));
+    RPKT_TRY(reframe_args_ok(b, recs_dev, max_payload, flags,
+                             RPKT_COALESCE_TRUST_SUMS | RPKT_COALESCE_UDP, out_frames_dev, out_bytes,
+                             out_offsets_dev, out_cap, src_first_dev, totals_dev, workspace_dev));
     if (b->n == 0) return RPKT_OK;
 
     const uint32_t n = b->n, nb = blocks(n), fb = (uint32_t)b->frames_bytes;
     const CoWs ws = co_ws(workspace_dev, n);
     hipStream_t st = (hipStream_t)stream;
     const dim3 blk(kSegBlock), per(nb);
-    RPKT_TRY(launch_batch(coalesce_plan_kernel, kSegBlock, 0, stream, *b, recs_dev, order_dev,
-                          flags & RPKT_COALESCE_TRUST_SUMS, ws.plan));
-    RPKT_TRY(launch(coalesce_link_kernel, per, blk, 0, st, b->frames_dev, fb, n, ws.plan, ws.aux,
+    const bool udp = (flags & RPKT_COALESCE_UDP) != 0u;
+    RPKT_TRY(launch_batch(udp ? coalesce_plan_kernel<true> : coalesce_plan_kernel<false>, kSegBlock, 0,
+                          stream, *b, recs_dev, order_dev, flags & RPKT_COALESCE_TRUST_SUMS, ws.plan));
+    RPKT_TRY(launch(udp ? coalesce_link_kernel<true> : coalesce_link_kernel<false>, per, blk, 0, st, b->frames_dev, fb, n, ws.plan, ws.aux,
                     ws.pmax));
     RPKT_TRY(launch(coalesce_scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
     RPKT_TRY(launch(coalesce_group_kernel, per, blk, 0, st, n, max_payload, ws.plan, ws.aux, ws.pmax,
@@ -499,7 +530,7 @@ int rpkt_gpu_coalesce_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                     (uint32_t)out_bytes, out_cap, ws.aux));
     const uint64_t hper = (uint64_t)kWavesPerBlock * kCoHdrRun;          // outputs a block
     const uint32_t outs = n < out_cap ? n : out_cap;                     // n_out <= both, or overflow
-    return launch(coalesce_header_kernel, dim3((uint32_t)(((uint64_t)outs + hper - 1) / hper)), blk,
+    return launch(udp ? coalesce_header_kernel<true> : coalesce_header_kernel<false>, dim3((uint32_t)(((uint64_t)outs + hper - 1) / hper)), blk,
                   0, st, b->frames_dev, fb, n, ws.plan, ws.obase, ws.aux, src_first_dev, totals_dev,
                   out_frames_dev, (uint32_t)out_bytes, out_cap);
 }

@@ -1,8 +1,9 @@
 // rpkt_segcopy.h — what the two units that re-frame a batch share (rpkt_segment.hip: one
 // frame into many; rpkt_coalesce.hip: many into one).  Host: the entries' argument checks and
-// the carving of their workspaces.  Device: what a record says about a TCP frame, a tile's
-// records staged through LDS, header sums by one lane, the block scans of the plan -> scan ->
-// write structure, and the wave copy between any two byte phases that sums what it copies.
+// the carving of their workspaces.  Device: what a record says about a TCP or UDP frame, a
+// tile's records staged through LDS, header sums by one lane, the block scans of the plan ->
+// scan -> write structure, and the wave copy between any two byte phases that sums what it
+// copies.
 // Everything is inline in an anonymous namespace.
 #pragma once
 #include "rpkt_common.h"
@@ -67,31 +68,43 @@ struct Carve {
     size_t used() const { return (size_t)(at - base); }
 };
 
-// What the record's dwords 0, 5, 7, 8, 16, 17 say about a frame of `len` bytes: `tcp`, status
-// OK and an unfragmented TCP packet over IPv4 or IPv6 whose offsets nest; pl clamped to the frame.
-struct TcpWhere {
-    bool tcp, v6;
+// What the record's dwords 0, 5, 7, 8, 16, 17 say about a frame of `len` bytes: `on`, status
+// OK and an unfragmented TCP packet (or, with `with_udp`, UDP datagram: `udp`) over IPv4 or
+// IPv6 whose offsets nest; pl clamped to the frame.  Without `with_udp` a UDP frame is as any
+// other protocol's: not `on`.
+struct L4Where {
+    bool on, udp, v6;
     uint32_t l3, l4, po, pl, pdst;
 };
-__device__ __forceinline__ TcpWhere tcp_where(uint32_t w0, uint32_t w5, uint32_t w7, uint32_t w8,
-                                              uint32_t w16, uint32_t w17, uint32_t len) {
+__device__ __forceinline__ L4Where l4_where(uint32_t w0, uint32_t w5, uint32_t w7, uint32_t w8,
+                                            uint32_t w16, uint32_t w17, uint32_t len, bool with_udp) {
     const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
     const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
     const bool v6 = det == 0x86ddu;
     const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
     const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16, po = w17 & 0xffffu;
-    // offsets that nest as a parse of this frame leaves them; [po, + pl) inside the frame
-    const bool nest = l4 >= l3 && po >= l4 && po <= len && po - l4 >= 20u && po - l4 <= 60u &&
+    const bool udp = with_udp && proto == 17u;
+    // offsets that nest as a parse of this frame leaves them (the L4 header: TCP's 20..60
+    // bytes, UDP's 8); [po, + pl) inside the frame
+    const bool nest = l4 >= l3 && po >= l4 && po <= len &&
+                      (udp ? po - l4 == 8u : (po - l4 >= 20u && po - l4 <= 60u)) &&
                       (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u));
     uint32_t pl = w17 >> 16;
     if (nest && pl > len - po) pl = len - po;
-    const bool tcp = status == RPKT_S_OK && proto == 6u && (v6 || det == 0x0800u) &&
-                     (v6 || (frag & 0x3fffu) == 0u) && nest;
-    return TcpWhere{tcp, v6, l3, l4, po, pl, pdst};
+    const bool on = status == RPKT_S_OK && (proto == 6u || udp) && (v6 || det == 0x0800u) &&
+                    (v6 || (frag & 0x3fffu) == 0u) && nest;
+    return L4Where{on, udp, v6, l3, l4, po, pl, pdst};
 }
 // the same from a staged record (stage_records_tile)
-__device__ __forceinline__ TcpWhere tcp_where(const uint32_t* w, uint32_t len) {
-    return tcp_where(w[0], w[5], w[7], w[8], w[16], w[17], len);
+__device__ __forceinline__ L4Where l4_where(const uint32_t* w, uint32_t len, bool with_udp) {
+    return l4_where(w[0], w[5], w[7], w[8], w[16], w[17], len, with_udp);
+}
+
+// The UDP checksum field for a one's complement sum over pseudo header, header and payload:
+// a result of 0 is sent as 0xffff (RFC 768), the opposite of TCP's, where 0 stays 0.
+__device__ __forceinline__ uint32_t udp_csum_field(uint32_t sum) {
+    const uint32_t ck = ~fold16(sum) & 0xffffu;
+    return ck ? ck : 0xffffu;
 }
 
 // The IPv6 pseudo header's destination: the routing header's final address when ip6_pdst_off

@@ -1,7 +1,12 @@
 // rpkt_segment.hip — rpkt_gpu_segment_batch and rpkt_gpu_segment_chains: TCP segmentation
 // (TSO) of a device-resident batch, flat or in mbuf chains, the TCP_SEG transmit offload of
-// rpkt-dpdk/examples/tso_tx.rs:128-134 under the Linux tcp_gso_segment / DPDK rte_gso rules
-// (include/rpkt_gpu.h has the semantics).
+// rpkt-dpdk/examples/tso_tx.rs:128-134 under the Linux tcp_gso_segment / DPDK rte_gso rules,
+// and with RPKT_SEGMENT_UDP UDP segmentation under the Linux __udp_gso_segment rules
+// (include/rpkt_gpu.h has the semantics).  UDP is a second L4 header rule in the same
+// kernels: another constant sum in the plan, one patch (length and checksum) where TCP has
+// three (seq, flags, checksum) in the write.  The kernels that test the protocol take the flag
+// as a template argument <kUdp>: a call with the flag clear launches the code without the
+// test, so the TCP-only call costs what it did before the flag existed.
 //
 // The output batch has another frame count and other offsets than the input, so the work
 // is planned from the input and split by the output.  Four launches on the stream, no host
@@ -11,7 +16,8 @@
 //             workspace, with the block's sums, and for a segmented frame the constants
 //             every one of its segments shares (the IPv4 header sum without packet_len /
 //             ident / checksum, the TCP header + pseudo header sum without seq / flags /
-//             checksum / length), read from the frame once per super-frame;
+//             checksum / length, or the UDP one without length / checksum), read from the
+//             frame once per super-frame;
 //   2. scan   exclusive prefix sums of counts and bytes: one block over the block sums
 //             (with a carry from each 256 to the next), then one block per 256 frames;
 //   3. write  one wavefront per run of kSegRun consecutive OUTPUT frames: it finds the first
@@ -21,9 +27,10 @@
 //             loads and a byte funnel shift per chunk), sums the bytes it copies (absolute
 //             destination phase, be_sum), and then writes the header with the patched fields
 //             and the two checksums.  A pass-through frame is the same copy without the sum.
-// What a record says about a TCP frame (tcp_where), the record stage, the block scan and the
-// kernel over the block sums, the copy, the header write, the entries' argument checks and the
-// workspace carving are in rpkt_segcopy.h, which rpkt_coalesce.hip (the inverse entry) shares.
+// What a record says about a TCP or UDP frame (l4_where), the record stage, the block scan and
+// the kernel over the block sums, the copy, the header write, the entries' argument checks and
+// the workspace carving are in rpkt_segcopy.h, which rpkt_coalesce.hip (the inverse entry)
+// shares.
 // Every load goes through the frames buffer resource and every store through one over
 // [out_frames_dev, + out_bytes); an overflowing batch (totals past the capacities) writes
 // its totals and seg_first and nothing else.
@@ -62,9 +69,9 @@ inline SegWs seg_ws(void* ws, uint32_t n) {
 
 // plan words: 0 frame offset (chains: the chain's first segment, clamped), 1 frame length
 // (chains: pkt_len), 2 l3 | l4 << 16, 3 payload_off | payload_len << 16, 4 IPv4 constant sum |
-// ident << 16, 5 TCP constant sum | be16 of TCP bytes 12..13 << 16, 6 seq, 7 bit 0 segmented,
-// bit 1 IPv6
-constexpr uint32_t kSegOn = 1u, kSegV6 = 2u;
+// ident << 16, 5 L4 constant sum | be16 of TCP bytes 12..13 << 16 (UDP: 0), 6 seq (UDP: 0),
+// 7 bit 0 segmented, bit 1 IPv6, bit 2 UDP
+constexpr uint32_t kSegOn = 1u, kSegV6 = 2u, kSegUdp = 4u;
 
 // ---- 1. plan ---------------------------------------------------------------------------
 
@@ -82,7 +89,7 @@ struct FlatHeader {
 // Plan words 2..7 of a segmented frame from its header H: the constants all its segments
 // share.
 template <class Header>
-__device__ __forceinline__ void seg_constants(const Header& H, const TcpWhere& s, uint32_t (&p)[8]) {
+__device__ __forceinline__ void seg_constants(const Header& H, const L4Where& s, uint32_t (&p)[8]) {
     const uint32_t l3 = s.l3, l4 = s.l4, po = s.po;
     // a field leaves a sum by adding its complement (one's complement arithmetic;
     // the sums stay positive, so the folded values are the plain sums')
@@ -98,17 +105,24 @@ __device__ __forceinline__ void seg_constants(const Header& H, const TcpWhere& s
         const uint32_t pd = ip6_pseudo_dst(s.pdst, l3, l4);
         pseudo = H.sum(l3 + 8u, l3 + 24u) + H.sum(pd, pd + 16u);
     }
-    const uint32_t t1 = H.dw(l4 + 4u), t3 = H.dw(l4 + 12u);
-    const uint32_t t4 = H.dw(l4 + 16u);
-    const uint32_t seq = bswap32(t1), w12 = be16_lo(t3);
-    const uint32_t tcpc = H.sum(l4, po) + pseudo + 6u + (0xffffu ^ (seq >> 16)) +
-                          (0xffffu ^ (seq & 0xffffu)) + (0xffffu ^ w12) + (0xffffu ^ be16_lo(t4));
+    // bytes l4 + 4..7 leave the L4 sum whole: TCP's seq, UDP's length and checksum
+    const uint32_t t1 = H.dw(l4 + 4u);
+    uint32_t l4c = H.sum(l4, po) + pseudo + (0xffffu ^ be16_lo(t1)) + (0xffffu ^ be16_hi(t1));
+    uint32_t seq = 0, w12 = 0;
+    if (s.udp) {
+        l4c += 17u;
+    } else {
+        const uint32_t t3 = H.dw(l4 + 12u), t4 = H.dw(l4 + 16u);
+        seq = bswap32(t1);
+        w12 = be16_lo(t3);
+        l4c += 6u + (0xffffu ^ w12) + (0xffffu ^ be16_lo(t4));
+    }
     p[2] = l3 | (l4 << 16);
     p[3] = po | (s.pl << 16);
     p[4] = fold16(ipc) | (ident << 16);
-    p[5] = fold16(tcpc) | (w12 << 16);
+    p[5] = fold16(l4c) | (w12 << 16);
     p[6] = seq;
-    p[7] = kSegOn | (s.v6 ? kSegV6 : 0u);
+    p[7] = kSegOn | (s.v6 ? kSegV6 : 0u) | (s.udp ? kSegUdp : 0u);
 }
 
 // The plan's end: frame i's plan, count and bytes to the workspace, the block's sums to part.
@@ -126,6 +140,7 @@ __device__ __forceinline__ void plan_store(bool valid, uint32_t i, const uint32_
     block_sums_to_part(cnt, bytes, part, red);
 }
 
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void segment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
                          const uint32_t* __restrict__ offsets, uint32_t stride, uint32_t frame_len,
@@ -146,14 +161,14 @@ void segment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         uint32_t* st = stage[wave];
         stage_records_tile(st, recs, p0, n, lane);
         const Frame fr = valid ? frame_span(offsets, stride, frame_len, fb, i) : Frame{0u, 0u};
-        const TcpWhere s = tcp_where(st + lane * 21, fr.len);
+        const L4Where s = l4_where(st + lane * 21, fr.len, kUdp);
         p[0] = fr.off;
         p[1] = fr.len;
         if (valid) {
             cnt = 1;
             bytes = fr.len;
         }
-        if (valid && s.tcp && s.pl > mss) {                       // segmented
+        if (valid && s.on && s.pl > mss) {                       // segmented
             cnt = (s.pl + mss - 1u) / mss;
             bytes = cnt * s.po + s.pl;
             seg_constants(FlatHeader{make_rsrc(frames, fb), fb, fr.off}, s, p);
@@ -222,6 +237,7 @@ __device__ __forceinline__ void chain_range(const uint32_t* __restrict__ chain_f
     b = b < n_segs ? b : n_segs;
 }
 
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void segment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
                                 const uint32_t* __restrict__ segs, uint32_t n_segs,
@@ -256,14 +272,14 @@ void segment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
         // a chain of 4 GiB or more cannot fit out_bytes: the call overflows and the write
         // never sees this plan; the record's offsets are 16 bits wide, so saturating is exact
         const uint32_t len = pkt < 0xffffffffull ? (uint32_t)pkt : 0xffffffffu;
-        const TcpWhere s = tcp_where(st + lane * 21, len);
+        const L4Where s = l4_where(st + lane * 21, len, kUdp);
         p[0] = a;
         p[1] = len;
         if (valid) {
             cnt = 1;
             bytes = pkt;
         }
-        if (valid && s.tcp && s.pl > mss) {                       // segmented
+        if (valid && s.on && s.pl > mss) {                       // segmented
             cnt = (s.pl + mss - 1u) / mss;
             bytes = cnt * s.po + s.pl;
             const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
@@ -319,6 +335,7 @@ __device__ __forceinline__ SegOut seg_out(u32x4 pa, u32x4 pb, uint32_t mss, uint
 }
 
 // The fields output k's header differs in, `pay` the big-endian sum of its payload.
+template <bool kUdp>
 __device__ __forceinline__ void seg_patches(const SegOut& o, u32x4 pb, uint32_t k, uint32_t pay,
                                             SegPatch (&P)[kSegPatches]) {
     const uint32_t l3 = o.l3, l4 = o.l4, po = o.po, pk = o.pk;
@@ -330,6 +347,14 @@ __device__ __forceinline__ void seg_patches(const SegOut& o, u32x4 pb, uint32_t 
     } else {
         P[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + pk) & 0xffffu)};
         P[1] = SegPatch{0u, 0u, 0u};
+    }
+    if (kUdp && (pb.w & kSegUdp)) {                               // wave-uniform: one output a wave
+        // length and checksum, one patch; the length is in the pseudo header and in the header
+        const uint32_t ulen = 8u + pk;
+        const uint32_t uck = udp_csum_field((pb.y & 0xffffu) + 2u * ulen + pay);
+        P[2] = SegPatch{l4 + 4u, 4u, bswap16(ulen) | (bswap16(uck) << 16)};
+        P[3] = P[4] = SegPatch{0u, 0u, 0u};
+        return;
     }
     const uint32_t seq = pb.z + o.done;
     uint32_t w12 = pb.y >> 16;
@@ -345,6 +370,7 @@ __device__ __forceinline__ void seg_patches(const SegOut& o, u32x4 pb, uint32_t 
 
 // Output j, the k-th of the input frame with plan (pa, pb) and output byte base `base`: its
 // offset entry and its bytes, the whole wave.
+template <bool kUdp>
 __device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
                                              __amdgpu_buffer_rsrc_t ro,
                                              uint32_t* __restrict__ out_offsets, uint32_t mss,
@@ -364,7 +390,7 @@ __device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t
     const uint32_t part = wave_copy<true>(rs, fb, ro, foff + o.po + o.done, o.d0 + o.po, o.pk, lane);
     const uint32_t pay = be_sum(wave_sum(fold16(part)), o.d0 + o.po);
     SegPatch P[kSegPatches];
-    seg_patches(o, pb, k, pay, P);
+    seg_patches<kUdp>(o, pb, k, pay, P);
     wave_copy_header(rs, fb, ro, foff, o.d0, o.po, hfirst, P, lane);
 }
 
@@ -414,6 +440,7 @@ __device__ __forceinline__ bool output_run(uint32_t n, const uint32_t* __restric
     return true;
 }
 
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n, uint32_t mss,
                           const u32x4* __restrict__ plan, const uint32_t* __restrict__ seg_first,
@@ -439,7 +466,7 @@ void segment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
             pb = plan[2 * (size_t)i + 1];
             base = (uint32_t)obase[i];
         }
-        write_output(rs, fb, ro, out_offsets, mss, j, j - cur, pa, pb, base, lane);
+        write_output<kUdp>(rs, fb, ro, out_offsets, mss, j, j - cur, pa, pb, base, lane);
     }
 }
 
@@ -504,6 +531,7 @@ __device__ __forceinline__ ChainState chain_state(const u32x4* __restrict__ plan
     return st;
 }
 
+template <bool kUdp>
 __device__ __forceinline__ void write_chain_output(__amdgpu_buffer_rsrc_t rs, const SegTable& S,
                                                    uint32_t n_segs, __amdgpu_buffer_rsrc_t ro,
                                                    uint32_t* __restrict__ out_offsets, uint32_t mss,
@@ -527,10 +555,11 @@ __device__ __forceinline__ void write_chain_output(__amdgpu_buffer_rsrc_t rs, co
                                            o.pk, lane);
     const uint32_t pay = be_sum(wave_sum(fold16(part)), o.d0 + o.po);
     SegPatch P[kSegPatches];
-    seg_patches(o, st.pb, k, pay, P);
+    seg_patches<kUdp>(o, st.pb, k, pay, P);
     wave_copy_header_from(ro, o.d0, o.po, hfirst, P, lane, fetch);
 }
 
+template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
 void segment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
                                  const uint32_t* __restrict__ segs, uint32_t n_segs, uint32_t n,
@@ -557,7 +586,7 @@ void segment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
             }
             st = chain_state(plan, obase, i, S, n_segs);
         }
-        write_chain_output(rs, S, n_segs, ro, out_offsets, mss, j, j - cur, st, lane);
+        write_chain_output<kUdp>(rs, S, n_segs, ro, out_offsets, mss, j, j - cur, st, lane);
     }
 }
 
@@ -585,14 +614,15 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev, ui
                            uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                            uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                            uint64_t* totals_dev, void* workspace_dev, void* stream) {
-    RPKT_TRY(reframe_args_ok(b, recs_dev, mss, flags, 0u, out_frames_dev, out_bytes, out_offsets_dev,
-                             out_cap, seg_first_dev, totals_dev, workspace_dev));
+    RPKT_TRY(reframe_args_ok(b, recs_dev, mss, flags, RPKT_SEGMENT_UDP, out_frames_dev, out_bytes,
+                             out_offsets_dev, out_cap, seg_first_dev, totals_dev, workspace_dev));
     if (b->n == 0) return RPKT_OK;
 
     const SegWs ws = seg_ws(workspace_dev, b->n);
-    RPKT_TRY(launch_batch(segment_plan_kernel, kSegBlock, 0, stream, *b, recs_dev, mss, ws.plan,
-                          seg_first_dev, ws.obase, ws.part));
-    return scan_and_write(segment_write_kernel, ws, b->n, out_cap, seg_first_dev, totals_dev,
+    const bool udp = (flags & RPKT_SEGMENT_UDP) != 0u;
+    RPKT_TRY(launch_batch(udp ? segment_plan_kernel<true> : segment_plan_kernel<false>, kSegBlock, 0,
+                          stream, *b, recs_dev, mss, ws.plan, seg_first_dev, ws.obase, ws.part));
+    return scan_and_write(udp ? segment_write_kernel<true> : segment_write_kernel<false>, ws, b->n, out_cap, seg_first_dev, totals_dev,
                           (hipStream_t)stream, b->frames_dev, (uint32_t)b->frames_bytes, b->n, mss,
                           ws.plan, seg_first_dev, ws.obase, totals_dev, out_frames_dev,
                           (uint32_t)out_bytes, out_offsets_dev, out_cap);
@@ -604,17 +634,19 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* c, const rpkt_rec_t* recs_dev, 
                             uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                             uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                             uint64_t* totals_dev, void* workspace_dev, void* stream) {
-    RPKT_TRY(reframe_args_ok(c, recs_dev, mss, flags, 0u, out_frames_dev, out_bytes, out_offsets_dev,
-                             out_cap, seg_first_dev, totals_dev, workspace_dev));
+    RPKT_TRY(reframe_args_ok(c, recs_dev, mss, flags, RPKT_SEGMENT_UDP, out_frames_dev, out_bytes,
+                             out_offsets_dev, out_cap, seg_first_dev, totals_dev, workspace_dev));
     if (c->n_chains == 0) return RPKT_OK;
 
     const uint32_t n = c->n_chains, fb = (uint32_t)c->buf_bytes;
     const uint32_t* segs = c->segs_dev;
     const SegWs ws = seg_ws(workspace_dev, n);
-    RPKT_TRY(launch(segment_chains_plan_kernel, dim3(blocks(n)), dim3(kSegBlock), 0,
-                    (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, c->chain_first_dev, n,
-                    recs_dev, mss, ws.plan, seg_first_dev, ws.obase, ws.part));
-    return scan_and_write(segment_chains_write_kernel, ws, n, out_cap, seg_first_dev, totals_dev,
+    const bool udp = (flags & RPKT_SEGMENT_UDP) != 0u;
+    RPKT_TRY(launch(udp ? segment_chains_plan_kernel<true> : segment_chains_plan_kernel<false>,
+                    dim3(blocks(n)), dim3(kSegBlock), 0, (hipStream_t)stream, c->buf_dev, fb, segs,
+                    c->n_segs, c->chain_first_dev, n, recs_dev, mss, ws.plan, seg_first_dev, ws.obase,
+                    ws.part));
+    return scan_and_write(udp ? segment_chains_write_kernel<true> : segment_chains_write_kernel<false>, ws, n, out_cap, seg_first_dev, totals_dev,
                           (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, n, mss, ws.plan,
                           seg_first_dev, ws.obase, totals_dev, out_frames_dev, (uint32_t)out_bytes,
                           out_offsets_dev, out_cap);

@@ -624,8 +624,11 @@ def _reframe_outputs(what, src, recs, cap_bound, bytes_bound, out_frames, out_of
     return out_frames, out_bytes, out_offsets, out_cap, first, totals, workspace
 
 
+SEGMENT_UDP = 16
+
+
 def _segment(name, src, what, recs, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
-             totals, workspace, stream, header_max):
+             totals, workspace, stream, header_max, udp):
     """segment_batch and segment_chains: `src` (a DeviceBatch or DeviceChains) cut at `mss`
     into a packed DeviceBatch; the default sizes from the documented bound over src's bytes."""
     n, fbytes = src.n, src.frames.numel()
@@ -634,17 +637,18 @@ def _segment(name, src, what, recs, mss, out_frames, out_offsets, out_cap, out_b
         lambda cap: fbytes + (cap - n) * (134 if header_max is None else header_max),
         out_frames, out_offsets, out_cap, out_bytes, seg_first, "seg_first", totals, workspace,
         "segment")
-    _call(name, ctypes.byref(src.desc()), recs.data_ptr(), mss, 0, out_frames.data_ptr(), out_bytes,
-          out_offsets.data_ptr(), out_cap, seg_first.data_ptr(), totals.data_ptr(),
-          workspace.data_ptr(), _stream_ptr(stream))
+    _call(name, ctypes.byref(src.desc()), recs.data_ptr(), mss, SEGMENT_UDP if udp else 0,
+          out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, seg_first.data_ptr(),
+          totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
     return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
 
 
 def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=None,
                   out_bytes=None, seg_first=None, totals=None, workspace=None, stream=None,
-                  header_max=None):
+                  header_max=None, udp=False):
     """rpkt_gpu_segment_batch: TCP segmentation (TSO) of `batch` at `mss`, located by `recs`
-    (parse_batch's records of this batch).  Returns (out, seg_first, totals): `out` a packed
+    (parse_batch's records of this batch); with udp=True (RPKT_SEGMENT_UDP) UDP datagrams longer
+    than `mss` are cut too (UDP GSO).  Returns (out, seg_first, totals): `out` a packed
     DeviceBatch over out_cap slots (slots past totals[0] are empty frames), seg_first an int32
     tensor of n + 1 (the outputs of frame i are [seg_first[i], seg_first[i + 1])), totals an
     int64 tensor {n_out, out_bytes_needed}.  Nothing here reads the device: when totals
@@ -654,7 +658,8 @@ def segment_batch(batch, recs, mss, out_frames=None, out_offsets=None, out_cap=N
     header_max (the longest payload_off of the batch) 134 unless given: Ethernet, two tags and
     60-B IPv4 and TCP headers; give it for IPv6 frames with long extension chains."""
     return _segment("rpkt_gpu_segment_batch", batch, "segment_batch", recs, mss, out_frames,
-                    out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max)
+                    out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max,
+                    udp)
 
 
 def segment_chains_workspace(n, device="cuda"):
@@ -665,20 +670,22 @@ def segment_chains_workspace(n, device="cuda"):
 
 def segment_chains(chains, recs, mss, out_frames=None, out_offsets=None, out_cap=None,
                    out_bytes=None, seg_first=None, totals=None, workspace=None, stream=None,
-                   header_max=None):
+                   header_max=None, udp=False):
     """rpkt_gpu_segment_chains: segment_batch over mbuf chains (a DeviceChains), read in
-    place; `recs` are parse_chains' records of them.  The same return value: (out, seg_first,
-    totals), `out` a packed, flat DeviceBatch of wire frames.
+    place; `recs` are parse_chains' records of them, `udp` as for segment_batch.  The same
+    return value: (out, seg_first, totals), `out` a packed, flat DeviceBatch of wire frames.
     The default sizes are segment_batch's with the arena's size, chains.buf.numel(), for
     frames_bytes: that bounds the chains' bytes only when segments do not overlap and are
     not shared between chains; size the outputs yourself otherwise."""
     if workspace is None:
         workspace = segment_chains_workspace(chains.n, chains.buf.device)
     return _segment("rpkt_gpu_segment_chains", chains, "segment_chains", recs, mss, out_frames,
-                    out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max)
+                    out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max,
+                    udp)
 
 
 COALESCE_TRUST_SUMS = 1
+COALESCE_UDP = 16
 
 
 def coalesce_workspace(n, device="cuda"):
@@ -689,8 +696,9 @@ def coalesce_workspace(n, device="cuda"):
 
 def coalesce_batch(batch, recs, order=None, max_payload=65535, trust_sums=False, out_frames=None,
                    out_offsets=None, out_cap=None, out_bytes=None, src_first=None, out_mss=None,
-                   totals=None, workspace=None, stream=None):
-    """rpkt_gpu_coalesce_batch: TCP receive coalescing (GRO) of `batch`, located by `recs`
+                   totals=None, workspace=None, stream=None, udp=False):
+    """rpkt_gpu_coalesce_batch: TCP receive coalescing (GRO) of `batch`, with udp=True
+    (RPKT_COALESCE_UDP) of UDP datagrams too (UDP GRO), located by `recs`
     (parse_batch's records of this batch, with both sums unless trust_sums), the positions
     taken in `order` (an int32 tensor of n frame indices, e.g. flow_order's; None: frame
     order).  Returns (out, src_first, totals): `out` a packed DeviceBatch over out_cap slots
@@ -711,9 +719,9 @@ def coalesce_batch(batch, recs, order=None, max_payload=65535, trust_sums=False,
     if out_mss is not None and (out_mss.numel() < n or out_mss.element_size() != 2):
         raise RpktError("coalesce_batch: out_mss takes %d 16-bit entries" % n)
     _call("rpkt_gpu_coalesce_batch", ctypes.byref(batch.desc()), recs.data_ptr(), _ptr(order),
-          max_payload, COALESCE_TRUST_SUMS if trust_sums else 0, out_frames.data_ptr(), out_bytes,
-          out_offsets.data_ptr(), out_cap, src_first.data_ptr(), _ptr(out_mss), totals.data_ptr(),
-          workspace.data_ptr(), _stream_ptr(stream))
+          max_payload, (COALESCE_TRUST_SUMS if trust_sums else 0) | (COALESCE_UDP if udp else 0),
+          out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, src_first.data_ptr(),
+          _ptr(out_mss), totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
     return DeviceBatch(out_frames, out_cap, out_offsets), src_first, totals
 
 

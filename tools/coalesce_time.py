@@ -20,7 +20,15 @@ The split of the time between the eight kernels comes from a run of its own:
 
 The run also checks the output: 23 segments an output, every output the source super-frame
 byte for byte (but its TCP checksum field, which the source leaves 0), and a parse of the
-output with both sums finds every frame OK with valid IPv4 and TCP sums."""
+output with both sums finds every frame OK with valid IPv4 and TCP sums.
+
+    python tools/coalesce_time.py --udp [--out profiles/udp_reframe/coalesce_times.json]
+
+adds the same workload as UDP datagrams (tools/segment_time.py --udp's: a 42-byte header,
+32,768 B of payload, cut at 1448 with RPKT_SEGMENT_UDP) coalesced with RPKT_COALESCE_UDP, in
+the same interleaved rounds as the TCP leg (flags 0) and the device copy:
+`udp_over_tcp_per_byte` and `udp_over_copy_per_byte` are same-run ratios.  Every output must
+be the source datagram byte for byte but its checksum field, which the source leaves 0."""
 import argparse
 import json
 import os
@@ -32,18 +40,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from segment_time import HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, super_frames, time_legs  # noqa: E402
+from segment_time import (HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, UDP_HDR, super_frames, time_legs,  # noqa: E402
+                          udp_super_frames)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/coalesce/times.json")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--udp", action="store_true",
+                    help="also time RPKT_COALESCE_UDP on the same workload as UDP datagrams")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace or counter pass")
     a = ap.parse_args()
+    a.out = a.out or ("profiles/udp_reframe/coalesce_times.json" if a.udp else "profiles/coalesce/times.json")
     import torch
     from rpkt_amd import engine
     from rpkt_amd.records import as_records
@@ -90,6 +102,28 @@ def main():
         torch.cuda.synchronize()
         return
     legs = {"coalesce_batch": coalesce, "device_copy": copy, "segment_batch": segment}
+    if a.udp:
+        ulen, useg_bytes = UDP_HDR + PAYLOAD, n * (per * UDP_HDR + PAYLOAD)
+        usrcs, usegs, urecs = [], [], []
+        for seed in (47, 4747):
+            db = engine.DeviceBatch(torch.from_numpy(udp_super_frames(n, seed).reshape(-1)).to("cuda"), n,
+                                    stride=ulen)
+            usrcs.append(db)
+            sdb, _, tot = engine.segment_batch(db, engine.parse_batch(db, 0), MSS, out_cap=n_seg,
+                                               out_bytes=useg_bytes, udp=True)
+            assert tot.cpu().tolist() == [n_seg, useg_bytes]
+            usegs.append(sdb)
+            urecs.append(engine.parse_batch(sdb, 3))
+        udp_out = torch.empty(n * ulen, dtype=torch.uint8, device="cuda")
+        udp_offsets, udp_first = torch.empty_like(out_offsets), torch.empty_like(first)
+        udp_mss, udp_totals = torch.empty_like(out_mss), torch.zeros_like(totals)
+
+        def coalesce_udp(k):
+            engine.coalesce_batch(usegs[k % R], urecs[k % R], out_frames=udp_out, out_offsets=udp_offsets,
+                                  out_cap=n, out_bytes=n * ulen, src_first=udp_first, out_mss=udp_mss,
+                                  totals=udp_totals, workspace=ws, stream=stream, udp=True)
+
+        legs = {"coalesce_udp": coalesce_udp, **legs}
     med, ms = time_legs(torch, stream, legs, a.launches, a.rounds)
 
     # the output is the source (checked on both batches)
@@ -109,6 +143,19 @@ def main():
         assert (orec["status"] == 0).all() and (orec["ip_sum"] == 0xffff).all()
         assert (orec["l4_sum"] == 0xffff).all() and (orec["payload_len"] == PAYLOAD).all()
 
+    for k in range(R if a.udp else 0):                            # the UDP output is its source too
+        udp_out.fill_(0xa5)
+        coalesce_udp(k)
+        torch.cuda.synchronize()
+        assert udp_totals.cpu().tolist() == [n, n * ulen], udp_totals.cpu().tolist()
+        assert torch.equal(udp_first[:n + 1], first[:n + 1]) and (udp_mss[:n] == MSS).all().item()
+        got, src = udp_out.view(n, ulen), usrcs[k].frames.view(n, ulen)
+        assert torch.equal(got[:, :40], src[:, :40]) and torch.equal(got[:, 42:], src[:, 42:])
+        urec = as_records(engine.parse_batch(engine.DeviceBatch(udp_out, n, udp_offsets), 3).cpu().numpy())
+        assert (urec["status"] == 0).all() and (urec["ip_protocol"] == 17).all()
+        assert (urec["ip_sum"] == 0xffff).all() and (urec["l4_sum"] == 0xffff).all()
+        assert (urec["payload_len"] == PAYLOAD).all()
+
     moved = {"frames_in": seg_bytes, "records_in": n_seg * 80, "offsets_in": (n_seg + 1) * 4,
              "frames_out": n * flen, "offsets_out": (n + 1) * 4, "src_first_out": (n_seg + 1) * 4,
              "out_mss_out": n_seg * 2}
@@ -122,7 +169,16 @@ def main():
     for name, b in (("coalesce_batch", alg), ("device_copy", 2 * seg_bytes), ("segment_batch", seg_alg)):
         res["ms"][name]["bytes"] = b
         res["ms"][name]["fraction_of_8TBs"] = round(b / (med[name] * 1e-3) / HBM_BYTES_PER_S, 4)
+    if a.udp:
+        ualg = alg - seg_bytes - n * flen + useg_bytes + n * ulen
+        res["udp"] = {"frame_len": ulen, "bytes": ualg}
+        res["ms"]["coalesce_udp"]["bytes"] = ualg
+        res["ms"]["coalesce_udp"]["fraction_of_8TBs"] = round(
+            ualg / (med["coalesce_udp"] * 1e-3) / HBM_BYTES_PER_S, 4)
     per_byte = {name: med[name] / res["ms"][name]["bytes"] for name in legs}
+    if a.udp:
+        res["udp_over_tcp_per_byte"] = round(per_byte["coalesce_udp"] / per_byte["coalesce_batch"], 4)
+        res["udp_over_copy_per_byte"] = round(per_byte["coalesce_udp"] / per_byte["device_copy"], 4)
     res["coalesce_over_copy_per_byte"] = round(per_byte["coalesce_batch"] / per_byte["device_copy"], 4)
     res["segment_over_copy_per_byte"] = round(per_byte["segment_batch"] / per_byte["device_copy"], 4)
     res["coalesce_over_segment_per_byte"] = round(

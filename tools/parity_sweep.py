@@ -15,9 +15,12 @@ and a config 13 / 14 batch), the layer walk; (b) a generator batch of a random c
 build with random checksum flags over its (IPv4 and IPv6) records, the forward with and
 without RPKT_F_IPV6, and the encapsulation build over a tunnel batch (configs 13 / 14); (c)
 a fuzzed mbuf-chain batch (configs 8 / 12) through the chain
-parse, another one through rpkt_gpu_segment_chains at a random mss against
-tests/segment_chains_model.py (the chain parse's records, or the flat oracle's of the
-flattened bytes, which gather headers across the cuts), and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
+parse, another one through rpkt_gpu_segment_chains at a random mss, with or without
+RPKT_SEGMENT_UDP, against tests/udp_reframe_model.py on the flattened chains (the chain
+parse's records, or the flat oracle's of the flattened bytes, which gather headers across the
+cuts), a generator batch through rpkt_gpu_segment_batch and its output through
+rpkt_gpu_coalesce_batch with random flags (RPKT_SEGMENT_UDP, RPKT_COALESCE_UDP, TRUST_SUMS)
+against the same model, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
 random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py; (d)
 a nested tunnel batch (tests/nested_tunnel_ref.py's recipe: config 13 / 14 frames, frame k
 wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level passes
@@ -46,6 +49,7 @@ import segment_chains_model  # noqa: E402
 import segment_model  # noqa: E402
 import tunnel_chain_model  # noqa: E402
 import tunnel_frames  # noqa: E402
+import udp_reframe_model  # noqa: E402
 from test_gpu_parity import assert_same, assert_same16  # noqa: E402
 
 THREADS = min(16, os.cpu_count() or 1)
@@ -210,18 +214,61 @@ def check_segment_chains(rng, seed):
     kind = "chain" if rng.random() < 0.6 else "flat"
     recs = (segment_chains_model.chain_records if kind == "chain" else
             segment_chains_model.flat_records)(hc)
-    out, first, totals = segment_chains_model.segment_chains(hc, recs, mss)
+    udp = bool(rng.random() < 0.5)                              # RPKT_SEGMENT_UDP
+    out, first, totals = udp_reframe_model.segment(segment_chains_model.flatten(hc), recs, mss, udp)
     out_cap = int(totals[0]) + int(rng.integers(0, 9))
     out_bytes = int(totals[1]) + int(rng.integers(0, 40))
     d = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).copy()).cuda()
     odb, gs, gt = engine.segment_chains(engine.DeviceChains.from_host(hc), d, mss, out_cap=out_cap,
-                                        out_bytes=out_bytes)
+                                        out_bytes=out_bytes, udp=udp)
     blob, offs = segment_model.packed_output(out, out_cap)
     assert gt.cpu().numpy().view(np.uint64).tolist() == totals.tolist(), "segment_chains totals"
     assert np.array_equal(gs.cpu().numpy().view(np.uint32), first), "segment_chains seg_first"
     assert np.array_equal(odb.offsets.cpu().numpy().view(np.uint32), offs), "segment_chains offsets"
     assert np.array_equal(odb.frames.cpu().numpy()[:blob.size], blob), "segment_chains frames"
-    return {"cfg": cfg, "n": int(hc.n), "mss": mss, "records": kind, "n_out": int(totals[0])}
+    return {"cfg": cfg, "n": int(hc.n), "mss": mss, "records": kind, "udp": udp,
+            "n_out": int(totals[0])}
+
+
+def same_reframed(what, odb, g_first, g_totals, out, first, totals, out_cap):
+    """A re-framing call's outputs against a model's (out_frames, first, totals)."""
+    blob, offs = segment_model.packed_output(out, out_cap)
+    assert g_totals.cpu().numpy().view(np.uint64).tolist() == totals.tolist(), what + " totals"
+    assert np.array_equal(g_first.cpu().numpy().view(np.uint32), first), what + " first"
+    assert np.array_equal(odb.offsets.cpu().numpy().view(np.uint32), offs), what + " offsets"
+    assert np.array_equal(odb.frames.cpu().numpy()[:blob.size], blob), what + " frames"
+
+
+def check_segment_coalesce(rng, seed):
+    """rpkt_gpu_segment_batch with and without RPKT_SEGMENT_UDP at a random mss, then
+    rpkt_gpu_coalesce_batch of its output with random flags, each against
+    tests/udp_reframe_model.py."""
+    import torch
+    cfg = int(rng.choice([4, 5, 6, 11]))
+    hb = gen.make_batch(cfg, int(rng.integers(1, 3000)), seed=seed)
+    mss = int(rng.choice([7, 16, 17, 100, 300, 536, 1448, 65535]))
+    udp = bool(rng.random() < 0.5)
+    out, first, totals = udp_reframe_model.segment(hb, segment_model.oracle_records(hb), mss, udp)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    db = engine.DeviceBatch.from_host(hb)
+    odb, gs, gt = engine.segment_batch(db, engine.parse_batch(db, segment_model.F6), mss, out_cap=out_cap,
+                                       out_bytes=int(totals[1]) + int(rng.integers(0, 40)), udp=udp)
+    same_reframed("segment_batch", odb, gs, gt, out, first, totals, out_cap)
+    shb = segment_model.pack(out)
+    cudp, trust = bool(rng.random() < 0.5), bool(rng.random() < 0.3)
+    max_payload = int(rng.choice([1, 1000, 9000, 65535]))
+    cout, cfirst, ctot, cmss = udp_reframe_model.coalesce(shb, segment_model.oracle_records(shb), None,
+                                                          max_payload, trust, cudp)
+    cap = int(ctot[0]) + int(rng.integers(0, 9))
+    sdb = engine.DeviceBatch.from_host(shb)
+    gm = torch.zeros(shb.n, dtype=torch.int16, device="cuda")
+    cdb, gf, gt = engine.coalesce_batch(sdb, engine.parse_batch(sdb, segment_model.F6), None, max_payload,
+                                        trust, out_cap=cap, out_bytes=int(ctot[1]) + int(rng.integers(0, 40)),
+                                        out_mss=gm, udp=cudp)
+    same_reframed("coalesce_batch", cdb, gf, gt, cout, cfirst, ctot, cap)
+    assert np.array_equal(gm.cpu().numpy().view(np.uint16), cmss), "coalesce_batch out_mss"
+    return {"cfg": cfg, "n": int(hb.n), "mss": mss, "udp": udp, "coalesce_udp": cudp, "trust": trust,
+            "max_payload": max_payload, "n_seg": int(totals[0]), "n_out": int(ctot[0])}
 
 
 def check_tunnel_chains(rng, seed):
@@ -295,6 +342,8 @@ def main():
                 rec["chains"] = check_chains(rng, seed)
                 step = "segment_chains"
                 rec["segment_chains"] = check_segment_chains(rng, seed)
+                step = "segment_coalesce"
+                rec["segment_coalesce"] = check_segment_coalesce(rng, seed)
                 step = "tunnel_chains"
                 rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
                 step = "tunnel_next"

@@ -29,7 +29,14 @@ records from a parse of the chains.  The yardstick there is what a caller withou
 must do, flatten and then segment: segment_batch on the flat batch plus one device copy of
 the bytes (an ideal flatten costs at least that); `chains_over_flatten_then_segment` is
 t(segment_chains) / (t(segment_batch) + t(device_copy)).  The chains' output must equal the
-flat batch's, byte for byte."""
+flat batch's, byte for byte.
+
+    python tools/segment_time.py --udp [--out profiles/udp_reframe/segment_times.json]
+
+adds the same workload as UDP datagrams (a 42-byte header, 32,768 B of payload, mss 1448) cut
+with RPKT_SEGMENT_UDP, in the same interleaved rounds as the TCP leg (flags 0) and the device
+copy: `udp_over_tcp_per_byte` and `udp_over_copy_per_byte` are same-run ratios.  Its output is
+checked the same way: 23 segments a datagram, every one OK with valid IPv4 and UDP sums."""
 import argparse
 import json
 import os
@@ -41,6 +48,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HDR, PAYLOAD, MSS = 54, 32768, 1448
+UDP_HDR = 42
 HBM_BYTES_PER_S = 8e12
 
 
@@ -69,6 +77,23 @@ def super_frames(n, seed):
     f = np.frombuffer(np.random.default_rng(seed).bytes(n * (HDR + PAYLOAD)),
                       dtype=np.uint8).reshape(n, HDR + PAYLOAD).copy()
     f[:, :HDR] = hdr
+    return f
+
+
+def udp_super_frames(n, seed):
+    """(n, 42 + 32768) uint8: one header (the UDP checksum left 0: segmentation fills it
+    whatever it holds), random payload."""
+    hdr = super_frames(1, 0)[0, :UDP_HDR].copy()
+    tot = 28 + PAYLOAD
+    hdr[16:18] = (tot >> 8, tot & 255)
+    hdr[23] = 17
+    hdr[24:26] = 0
+    ck = rfc1071(hdr[14:34])
+    hdr[24:26] = (ck >> 8, ck & 255)
+    hdr[38:42] = ((8 + PAYLOAD) >> 8, (8 + PAYLOAD) & 255, 0, 0)
+    f = np.frombuffer(np.random.default_rng(seed).bytes(n * (UDP_HDR + PAYLOAD)),
+                      dtype=np.uint8).reshape(n, UDP_HDR + PAYLOAD).copy()
+    f[:, :UDP_HDR] = hdr
     return f
 
 
@@ -125,13 +150,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--chains", action="store_true",
                     help="also time rpkt_gpu_segment_chains on the same frames as mbuf chains")
+    ap.add_argument("--udp", action="store_true",
+                    help="also time RPKT_SEGMENT_UDP on the same workload as UDP datagrams")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace pass")
     a = ap.parse_args()
-    a.out = a.out or ("profiles/segment_chains/times.json" if a.chains else "profiles/segment/times.json")
+    a.out = a.out or ("profiles/udp_reframe/segment_times.json" if a.udp else
+                      "profiles/segment_chains/times.json" if a.chains else "profiles/segment/times.json")
     import torch
     from rpkt_amd import engine
     from rpkt_amd.records import as_records
@@ -177,6 +205,22 @@ def main():
                                   totals=chain_totals, workspace=cws, stream=stream)
 
         legs = {"segment_chains": segment_chains, **legs}
+    if a.udp:
+        ulen = UDP_HDR + PAYLOAD
+        uneed = n * (per * UDP_HDR + PAYLOAD)
+        udbs = [engine.DeviceBatch(torch.from_numpy(udp_super_frames(n, seed).reshape(-1)).to("cuda"), n,
+                                   stride=ulen) for seed in (47, 4747)]
+        urecs = [engine.parse_batch(db, 0) for db in udbs]
+        udp_out = torch.empty(uneed, dtype=torch.uint8, device="cuda")
+        udp_offsets, udp_first = torch.empty_like(out_offsets), torch.empty_like(seg_first)
+        udp_totals = torch.zeros_like(totals)
+
+        def segment_udp(k):
+            engine.segment_batch(udbs[k % R], urecs[k % R], MSS, out_frames=udp_out,
+                                 out_offsets=udp_offsets, seg_first=udp_first, totals=udp_totals,
+                                 workspace=ws, stream=stream, udp=True)
+
+        legs = {"segment_udp": segment_udp, **legs}
     if a.trace_launches:
         for k in range(a.trace_launches):
             (segment_chains if a.chains else segment)(k)
@@ -203,6 +247,17 @@ def main():
         torch.cuda.synchronize()
         assert torch.equal(chain_totals, totals) and torch.equal(chain_first, seg_first)
         assert torch.equal(chain_offsets, out_offsets) and torch.equal(chain_out, out_frames)
+
+    if a.udp:                                                     # the UDP workload is what it claims
+        segment_udp(0)
+        torch.cuda.synchronize()
+        assert udp_totals.cpu().tolist() == [n_out, uneed], udp_totals.cpu().tolist()
+        assert torch.equal(udp_first, seg_first)
+        urec = as_records(engine.parse_batch(engine.DeviceBatch(udp_out, n_out, udp_offsets), 3).cpu().numpy())
+        assert (urec["status"] == 0).all() and (urec["ip_protocol"] == 17).all()
+        assert (urec["ip_sum"] == 0xffff).all() and (urec["l4_sum"] == 0xffff).all()
+        assert (urec["payload_len"][~last] == MSS).all()
+        assert (urec["payload_len"][last] == PAYLOAD - (per - 1) * MSS).all()
 
     moved = {"frames_in": n * flen, "records_in": n * 80, "frames_out": need,
              "offsets_out": (n_out + 1) * 4}
@@ -231,6 +286,15 @@ def main():
         res["chains_over_flatten_then_segment"] = round(
             med["segment_chains"] / (med["segment_batch"] + med["device_copy"]), 4)
         res["chains_over_segment_batch"] = round(med["segment_chains"] / med["segment_batch"], 4)
+    if a.udp:
+        ualg = n * ulen + n * 80 + uneed + (n_out + 1) * 4
+        res["udp"] = {"frame_len": ulen, "bytes": ualg}
+        res["ms"]["segment_udp"]["bytes"] = ualg
+        res["ms"]["segment_udp"]["fraction_of_8TBs"] = round(
+            ualg / (med["segment_udp"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        res["udp_over_tcp_per_byte"] = round((med["segment_udp"] / ualg) / (med["segment_batch"] / alg), 4)
+        res["udp_over_copy_per_byte"] = round(
+            (med["segment_udp"] / ualg) / (med["device_copy"] / (2 * n * flen)), 4)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
