@@ -403,6 +403,18 @@ extern "C" {
                                    out_offsets_dev: *mut u32, out_cap: u32,
                                    seg_first_dev: *mut u32, totals_dev: *mut u64,
                                    workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_segment_tunnel_batch for n input frames.
+    pub fn rpkt_gpu_segment_tunnel_workspace_bytes(n: u32) -> usize;
+    /// Segmentation of the inner TCP (with RPKT_SEGMENT_UDP also UDP) of VXLAN, GTP-U and GRE
+    /// frames, located by rpkt_gpu_parse_tunnel_batch's three record arrays of the same batch:
+    /// the inner frame is cut as rpkt_gpu_segment_batch cuts it and the outer lengths and
+    /// checksums are fixed up; a frame without a tunnel is cut under its outer record.
+    pub fn rpkt_gpu_segment_tunnel_batch(batch: *const rpkt_batch_t, outer_dev: *const rpkt_rec_t,
+                                         tun_dev: *const rpkt_tun_t, inner_dev: *const rpkt_rec_t,
+                                         mss: u32, flags: u32, out_frames_dev: *mut u8,
+                                         out_bytes: u64, out_offsets_dev: *mut u32, out_cap: u32,
+                                         seg_first_dev: *mut u32, totals_dev: *mut u64,
+                                         workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
     /// Workspace of rpkt_gpu_coalesce_batch for n positions.
     pub fn rpkt_gpu_coalesce_workspace_bytes(n: u32) -> usize;
     /// TCP receive coalescing (GRO / LRO) on the device: consecutive in-order TCP segments of

@@ -492,6 +492,34 @@ pub unsafe fn segment_chains_flags(chains: &ffi::rpkt_chains_t, recs_dev: *const
                                        out.totals_dev, workspace_dev, stream))
 }
 
+/// rpkt_gpu_segment_tunnel_workspace_bytes: the workspace of segment_tunnel_batch for `n` input
+/// frames.
+pub fn segment_tunnel_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_segment_tunnel_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_segment_tunnel_batch: segmentation of the inner TCP (with `flags` =
+/// `ffi::RPKT_SEGMENT_UDP` also the inner UDP) of the VXLAN / GTP-U / GRE frames of a batch at
+/// `mss` (1..65535), the outer lengths and checksums fixed up; frames without a tunnel are cut
+/// as segment_batch_flags cuts them.  `out` is laid out as segment_batch's.
+///
+/// # Safety
+/// `batch` must describe device memory valid for the call; `outer_dev`, `tun_dev` and
+/// `inner_dev` must be what parse_tunnel_batch wrote for this same batch (16-byte aligned);
+/// every pointer of `out` must be device memory of the size its field documents, and
+/// `workspace_dev` must hold `segment_tunnel_workspace_bytes(batch.n)` bytes (16-byte aligned),
+/// all on the same device.
+pub unsafe fn segment_tunnel_batch(batch: &ffi::rpkt_batch_t, outer_dev: *const Rec,
+                                   tun_dev: *const ffi::rpkt_tun_t, inner_dev: *const Rec,
+                                   mss: u32, flags: u32, out: &SegmentOut,
+                                   workspace_dev: *mut core::ffi::c_void,
+                                   stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_segment_tunnel_batch(batch, outer_dev, tun_dev, inner_dev, mss, flags,
+                                             out.frames_dev, out.out_bytes, out.offsets_dev,
+                                             out.out_cap, out.seg_first_dev, out.totals_dev,
+                                             workspace_dev, stream))
+}
+
 /// The outputs of rpkt_gpu_coalesce_batch: a packed batch of `out_cap` slots (`frames_dev`,
 /// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first
 /// position of every output (`src_first_dev`, `n + 1` entries), each merged output's segment

@@ -112,6 +112,8 @@ enum rpkt_status {
  *     chain_first_dev, or with n_segs > 0 NULL buf_dev / segs_dev (E_INVAL); buf_bytes and
  *     n_segs (E_TOO_LARGE); out_bytes (E_TOO_LARGE); out_cap == 0 (E_INVAL); alignment
  *     (E_ALIGN): segs_dev and totals_dev 8 B, recs_dev, out_frames_dev, workspace_dev 16 B;
+ *   rpkt_gpu_segment_tunnel_batch: rpkt_gpu_segment_batch's order with outer_dev, tun_dev and
+ *     inner_dev in recs_dev's places: each required (E_INVAL) and 16-byte aligned (E_ALIGN);
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
@@ -779,8 +781,10 @@ int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uin
  * nest as a parse leaves them (l3_off + 20 (IPv6: 40) <= l4_off, l4_off + 20 <= payload_off
  * <= frame_len, header lengths within 60; UDP: l4_off + 8 == payload_off) passes through:
  * wrong frames, never a fault.
- * Not covered: the inner TCP or UDP of tunnelled frames, a segment size per flow, IPv4 UDP
- * fragmentation (UFO). */
+ * A tunnelled frame is to this entry what its outer record says: it passes through, and with
+ * RPKT_SEGMENT_UDP the OUTER datagram of a VXLAN / GTP-U frame would be cut, which destroys the
+ * tunnel; rpkt_gpu_segment_tunnel_batch (below) cuts the inner TCP or UDP instead.
+ * Not covered: a segment size per flow, IPv4 UDP fragmentation (UFO). */
 #define RPKT_SEGMENT_UDP  16u   /* also segment UDP datagrams (flags of both segment entries) */
 
 size_t rpkt_gpu_segment_workspace_bytes(uint32_t n);
@@ -824,12 +828,87 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev
  * rpkt_gpu_parse_batch over out_cap slots captures as one graph.
  * Bounds for sizing: rpkt_gpu_segment_batch's with the sum of the chains' pkt_len in
  * frames_bytes' place; that sum is at most buf_bytes when segments do not overlap.
- * Not covered: coalescing over chains, the inner TCP or UDP of tunnelled frames. */
+ * Not covered: coalescing over chains; the inner TCP or UDP of tunnelled frames over chains
+ * (rpkt_gpu_segment_tunnel_batch, below, takes flat batches only). */
 size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n_chains);
 int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_dev, uint32_t mss,
                             uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
                             uint32_t* out_offsets_dev, uint32_t out_cap, uint32_t* seg_first_dev,
                             uint64_t* totals_dev, void* workspace_dev, void* stream);
+
+/* Segmentation of the inner TCP / UDP of tunnels: what a VTEP or UPF needs to send a large
+ * application write through VXLAN, GTP-U or GRE without leaving the device.  Every NIC the
+ * reference targets pairs TSO with the tunnel offloads (rpkt-dpdk/src/conf.rs:80 lists
+ * DEV_TX_OFFLOAD_OUTER_IPV4_CKSUM next to TCP_TSO); Linux does this cut in
+ * skb_udp_tunnel_segment and gre_gso_segment.
+ *
+ * outer_dev, tun_dev, inner_dev: the three outputs of rpkt_gpu_parse_tunnel_batch on this same
+ * batch (level 1; RPKT_F_IPV6 for IPv6 at either level; the sum flags do not matter).  As for
+ * rpkt_gpu_segment_batch the records only locate things and every header byte is taken from the
+ * frame.  mss: 1..65535.  flags: 0 or RPKT_SEGMENT_UDP.  Below O, T, I are frame i's outer,
+ * tunnel and inner record; ipo = I.payload_off, ipl = I.payload_len clamped to the frame, toff =
+ * T.tun_off, ioff = T.inner_off.
+ *   No tunnel   T.kind == RPKT_TUN_NONE: the frame is handled exactly as
+ *               rpkt_gpu_segment_batch handles it with record O and the same mss and flags, so a
+ *               mixed transmit batch needs this one call only.
+ *   Undecoded   T.kind != NONE and T.status != RPKT_T_OK: the frame passes through, a byte copy
+ *               of [0, frame_len).  Its outer UDP is never cut, with or without the flag.
+ *   Decoded     the frame is segmented iff all of these hold; anything else passes through:
+ *               - I: status == RPKT_S_OK; ip_protocol 6, or with RPKT_SEGMENT_UDP 17 with
+ *                 payload_off - l4_off == 8; for IPv4 (ip_frag & 0x3fff) == 0; ipl > mss; its
+ *                 offsets, all positions in the outer frame, nest as rpkt_gpu_segment_batch
+ *                 requires;
+ *               - O: IPv4 or IPv6 by its dispatch ethertype; for IPv4 (ip_frag & 0x3fff) == 0;
+ *                 O.l3_off + 20 (IPv6: + 40) <= O.l4_off, an IPv4 header within 60 bytes;
+ *                 VXLAN / GTP-U: O.status == RPKT_S_OK, ip_protocol 17, O.l4_off + 8 <= toff;
+ *                 GRE: ip_protocol 47, O.l4_off == toff;
+ *               - toff + 8 (GRE: + 4, with the C bit + 8) <= ioff <= I.l3_off;
+ *               - GRE: the S (sequence) and R bits of the frame's byte toff are clear: Linux
+ *                 disables GSO on a GRE device with sequence numbers, a cut cannot invent them.
+ * A segmented frame yields n_i = ceil(ipl / mss) frames.  Segment k, with p_k as above and
+ * tot = ipo + p_k:
+ *   bytes       [0, ipo) of the frame, then payload bytes [ipo + k * mss, + p_k); nothing after
+ *               the inner IP packet's end is carried (inner and outer Ethernet padding);
+ *   inner       the inner IP and L4 headers exactly as rpkt_gpu_segment_batch writes them for
+ *               the inner frame on its own: IPv4 packet_len / ident + k / checksum or IPv6
+ *               payload_len; TCP seq / FIN, PSH, CWR / checksum, or UDP length / checksum;
+ *   GTP-U       length (bytes toff+2..3) = tot - toff - 8; sequence, N-PDU and extension
+ *               headers copied;
+ *   GRE         with the C bit the checksum word (bytes toff+4..5) is the RFC 2784 checksum
+ *               over [toff, tot) of the output, as rpkt_gpu_build_tunnel_batch fills it (a
+ *               result of 0 stays 0); without C nothing changes in the GRE header;
+ *   outer UDP   length = tot - O.l4_off.  A checksum field of 0 in the input stays 0 in every
+ *               output, over IPv4 and IPv6 alike (Linux keeps a tunnel's "no checksum"; RFC
+ *               6935 / 6936).  Otherwise it is filled over the outer pseudo header (the IPv6
+ *               destination under rpkt_gpu_build_batch's ip6_pdst_off rule) and
+ *               [O.l4_off, tot) of the output, a result of 0 written as 0xffff;
+ *   outer IPv4  packet_len = tot - O.l3_off; ident = (ident + k) & 0xffff; the header checksum
+ *               refilled;
+ *   outer IPv6  payload_len = tot - O.l3_off - 40; extension headers untouched.
+ * Length fields are taken mod 2^16.
+ * Outputs, overflow, the spare offset slots, the packed layout, "nothing written outside the
+ * buffers" and plan -> prefix sums -> write on `stream` with no host step are
+ * rpkt_gpu_segment_batch's contract word for word: rpkt_gpu_parse_tunnel_batch ->
+ * rpkt_gpu_segment_tunnel_batch -> rpkt_gpu_parse_tunnel_batch over out_cap slots captures as
+ * one graph.  Bounds for sizing: that entry's, with H the longest INNER payload_off of the
+ * batch.  workspace_dev: rpkt_gpu_segment_tunnel_workspace_bytes(n) bytes, 16-byte aligned.
+ * Argument checks: rpkt_gpu_segment_batch's in its order, with tun_dev and inner_dev required
+ * and 16-byte aligned along with outer_dev.
+ * The records must come from a parse of the same batch.  With other records the outputs are
+ * unspecified, but every load goes through the frames buffer resource and every store through
+ * the output's, and offsets that do not nest as above make the frame pass through: wrong
+ * frames, never a fault.
+ * Not covered: coalescing of tunnelled frames, tunnel segmentation over mbuf chains, nested
+ * tunnels (only the level-1 records are accepted: the inner frame of a second tunnel level is
+ * payload here), a segment size per flow, GRE sequence numbers, turning a zero outer UDP
+ * checksum into a filled one. */
+size_t rpkt_gpu_segment_tunnel_workspace_bytes(uint32_t n);
+int rpkt_gpu_segment_tunnel_batch(const rpkt_batch_t* batch, const rpkt_rec_t* outer_dev,
+                                  const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                  uint32_t mss, uint32_t flags, uint8_t* out_frames_dev,
+                                  uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
+                                  uint32_t* seg_first_dev, uint64_t* totals_dev, void* workspace_dev,
+                                  void* stream);
 
 /* ---- TCP and UDP receive coalescing (GRO / LRO, UDP GRO) --------------------------- */
 

@@ -133,13 +133,15 @@ def build_gen(force=False):
     return GEN_LIB
 
 
-EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "tso_tx_chains", "lro_rx")
+EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "tso_tx_chains", "lro_rx",
+            "vtep_tx")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "parse_batch")
 FLOW_REDUCE_BIN = os.path.join(ROOT, "examples", "flow_reduce")
 VTEP_RX_BIN = os.path.join(ROOT, "examples", "vtep_rx")
 TSO_TX_BIN = os.path.join(ROOT, "examples", "tso_tx")
 TSO_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "tso_tx_chains")
 LRO_RX_BIN = os.path.join(ROOT, "examples", "lro_rx")
+VTEP_TX_BIN = os.path.join(ROOT, "examples", "vtep_tx")
 
 
 def build_example(force=False):

@@ -32,20 +32,22 @@ inline bool source_misaligned(const rpkt_chains_t& c) { return misaligned(7, c.s
 
 // The checks of a re-framing entry in the documented order: required pointers, flags, `limit`
 // (mss, max_payload) in 1..65535, no inputs (RPKT_OK: the entry then returns), the source with
-// out_bytes, out_cap, alignment.
-template <class Source>
+// out_bytes, out_cap, alignment.  more_recs: an entry's further record arrays (the tunnel and
+// inner records of a tunnel entry), required and 16-byte aligned as recs is.
+template <class Source, typename... More>
 inline int reframe_args_ok(const Source* src, const rpkt_rec_t* recs, uint32_t limit,
                            uint32_t flags, uint32_t allowed, const uint8_t* out_frames,
                            uint64_t out_bytes, const uint32_t* out_offsets, uint32_t out_cap,
-                           const uint32_t* first, const uint64_t* totals, const void* workspace) {
-    if (!src || any_null(recs, out_frames, out_offsets, first, totals) || !workspace)
+                           const uint32_t* first, const uint64_t* totals, const void* workspace,
+                           const More*... more_recs) {
+    if (!src || any_null(recs, out_frames, out_offsets, first, totals, more_recs...) || !workspace)
         return RPKT_E_INVAL;
     RPKT_TRY(flags_ok(flags, allowed));
     if (limit == 0u || limit > 65535u) return RPKT_E_INVAL;
     if (source_n(*src) == 0) return RPKT_OK;
     RPKT_TRY(source_ok(*src, out_bytes));
     if (out_cap == 0u) return RPKT_E_INVAL;
-    if (source_misaligned(*src) || misaligned(15, recs, out_frames) ||
+    if (source_misaligned(*src) || misaligned(15, recs, out_frames, more_recs...) ||
         misaligned(15, (const uint8_t*)workspace) || misaligned(7, totals))
         return RPKT_E_ALIGN;
     return RPKT_OK;
@@ -322,7 +324,7 @@ __device__ __forceinline__ uint32_t wave_copy(__amdgpu_buffer_rsrc_t rs, uint32_
 struct SegPatch {
     uint32_t off, n, val;
 };
-constexpr int kSegPatches = 5;
+constexpr int kSegPatches = 5;     // a header's patches; an entry with more sizes its own array
 
 // The header [s0, s0 + len) goes to [d0, d0 + len) a lane per 4-B aligned destination dword
 // (headers are a few dwords: one pass as a rule).  header_dword: the source bytes of
@@ -335,11 +337,10 @@ __device__ __forceinline__ uint32_t header_dword(__amdgpu_buffer_rsrc_t rs, uint
 // Copy a `len`-byte header to [d0, d0 + len) with the patches applied.  fetch(c): the source
 // bytes of destination dword c, as header_dword gives them; `first`: fetch(lane), which the
 // caller loaded along with the payload.
-template <class Fetch>
+template <int N, class Fetch>
 __device__ __forceinline__ void wave_copy_header_from(__amdgpu_buffer_rsrc_t ro, uint32_t d0,
                                                       uint32_t len, uint32_t first,
-                                                      const SegPatch (&P)[kSegPatches], int lane,
-                                                      Fetch fetch) {
+                                                      const SegPatch (&P)[N], int lane, Fetch fetch) {
     const uint32_t dend = d0 + len;
     const uint32_t ndw = (dend - (d0 & ~3u) + 3u) >> 2;
     for (uint32_t c = (uint32_t)lane; c < ndw; c += kWave) {
@@ -347,7 +348,7 @@ __device__ __forceinline__ void wave_copy_header_from(__amdgpu_buffer_rsrc_t ro,
         const int rel = (int)(dd - d0);                 // header offset of the dword's byte 0
         uint32_t v = c < (uint32_t)kWave ? first : fetch(c);
 #pragma unroll
-        for (int k = 0; k < kSegPatches; ++k) {
+        for (int k = 0; k < N; ++k) {
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const uint32_t idx = (uint32_t)(rel + b) - P[k].off;
@@ -360,10 +361,11 @@ __device__ __forceinline__ void wave_copy_header_from(__amdgpu_buffer_rsrc_t ro,
 }
 
 // The same for a header that lies at [s0, s0 + len) of the frames buffer.
+template <int N>
 __device__ __forceinline__ void wave_copy_header(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
                                                  __amdgpu_buffer_rsrc_t ro, uint32_t s0,
                                                  uint32_t d0, uint32_t len, uint32_t first,
-                                                 const SegPatch (&P)[kSegPatches], int lane) {
+                                                 const SegPatch (&P)[N], int lane) {
     wave_copy_header_from(ro, d0, len, first, P, lane,
                           [&](uint32_t c) { return header_dword(rs, fb, s0, d0, c); });
 }

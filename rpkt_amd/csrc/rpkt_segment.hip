@@ -45,22 +45,27 @@
 // rpkt_gpu_parse_chains calls TCP: there a header may start where a segment ends but never
 // straddles an end), and byte by byte through the segment list otherwise, its sums then
 // taken at the logical position's parity.
+//
+// rpkt_gpu_segment_tunnel_batch (the inner TCP / UDP of VXLAN, GTP-U and GRE frames, flat
+// batches) is the flat cut with the inner record plus the outer headers' fix-ups: a plan and a
+// write kernel of its own with a 64-B plan and nine patches, everything else shared; see
+// "tunnels" below.
 #include "rpkt_segcopy.h"
 
 namespace {
 
-// the workspace: per-frame plans (32 B), per-frame output byte bases (u64), block sums
-// (count, bytes: u64 pairs)
+// the workspace: per-frame plans (32 B: `quads` 2; the tunnel entry's 64 B: 4), per-frame
+// output byte bases (u64), block sums (count, bytes: u64 pairs)
 struct SegWs {
     u32x4*    plan;
     uint64_t* obase;
     uint64_t* part;
     size_t    bytes;
 };
-inline SegWs seg_ws(void* ws, uint32_t n) {
+inline SegWs seg_ws(void* ws, uint32_t n, uint32_t quads = 2) {
     Carve c(ws);
     SegWs w;
-    w.plan = c.take<u32x4>(2 * (size_t)n);
+    w.plan = c.take<u32x4>(quads * (size_t)n);
     w.obase = c.take<uint64_t>(n);
     w.part = c.take<uint64_t>(2 * (size_t)blocks(n));
     w.bytes = c.used();
@@ -125,15 +130,17 @@ __device__ __forceinline__ void seg_constants(const Header& H, const L4Where& s,
     p[7] = kSegOn | (s.v6 ? kSegV6 : 0u) | (s.udp ? kSegUdp : 0u);
 }
 
-// The plan's end: frame i's plan, count and bytes to the workspace, the block's sums to part.
+// The plan's end: frame i's plan (words 0..7 of its kQuads * 16 bytes), count and bytes to the
+// workspace, the block's sums to part.
+template <int kQuads = 2>
 __device__ __forceinline__ void plan_store(bool valid, uint32_t i, const uint32_t (&p)[8],
                                            uint64_t cnt, uint64_t bytes, u32x4* __restrict__ plan,
                                            uint32_t* __restrict__ seg_first,
                                            uint64_t* __restrict__ obase, uint64_t* __restrict__ part,
                                            uint64_t* red) {
     if (valid) {
-        plan[2 * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
-        plan[2 * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
+        plan[kQuads * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
+        plan[kQuads * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
         seg_first[i] = (uint32_t)cnt;
         obase[i] = bytes;
     }
@@ -590,6 +597,276 @@ void segment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
     }
 }
 
+// ---- tunnels: the inner TCP / UDP of VXLAN, GTP-U and GRE frames ------------------------
+//
+// rpkt_gpu_segment_tunnel_batch cuts the inner frame of a decoded tunnel: the inner record's
+// offsets are positions in the outer frame, so the cut is the flat one with the inner record
+// -- the same copy, the same inner patches -- and the outer headers follow: the outer IP
+// length / ident / checksum, the outer UDP length and checksum (or the GRE checksum), the
+// GTP-U length.  The plan is 64 B a frame: words 0..7 as above for the inner frame (a frame
+// without a tunnel: for the frame itself, and the rest 0), then
+//   8 outer l3 | outer l4 << 16, 9 tun_off, 10 outer IPv4 constant sum | outer ident << 16,
+//   11 the outer L4 constant: the pseudo header (UDP) and [origin, payload_off) without the
+//      bytes the write patches, origin the outer UDP header or (GRE with C) the GRE header;
+//   word 7 also bit 3 a tunnel, bit 4 outer IPv6, bit 5 outer UDP (VXLAN, GTP-U; clear: GRE),
+//   bit 6 GTP-U, bit 7 the outer checksum is filled (UDP: the input's field is not 0; GRE: C).
+// The write forms the outer checksum from that constant, the values of the patches that lie
+// under it and the payload sum the copy returned for the inner checksum: the payload is
+// summed once.  A patch or the payload at an odd distance from the origin enters byte-swapped
+// (it cannot happen in a frame that parsed: every header in between is even).
+constexpr uint32_t kTunOn = 8u, kTunV6 = 16u, kTunUdp = 32u, kTunGtp = 64u, kTunCsum = 128u;
+constexpr int kTunPatches = 9;
+
+// What the outer record (dwords 0, 5, 7, 8, 16) and the tunnel record say about the carrier of
+// an inner frame at `in`: ok, the outer headers are ones the write can fix up and the offsets
+// nest (outer l3 + 20 (IPv6: 40) <= l4; VXLAN / GTP-U: status OK, protocol 17, l4 + 8 <=
+// tun_off; GRE: protocol 47, l4 == tun_off; tun_off + 8 (GRE: 4) <= inner_off <= inner l3).
+struct TunWhere {
+    bool ok, v6, udp, gtp;
+    uint32_t l3, l4, toff, ioff, pdst;
+};
+__device__ __forceinline__ TunWhere tun_where(uint32_t w0, uint32_t w5, uint32_t w7, uint32_t w8,
+                                              uint32_t w16, u32x4 t, const L4Where& in) {
+    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
+    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
+    const bool v6 = det == 0x86ddu;
+    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
+    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16;
+    const uint32_t kind = t.x & 0xffu, toff = t.x >> 16, ioff = t.y & 0xffffu;
+    const bool gre = kind == RPKT_TUN_GRE, gtp = kind == RPKT_TUN_GTPU;
+    const bool carrier = gre ? (proto == 47u && l4 == toff)
+                             : ((kind == RPKT_TUN_VXLAN || gtp) && status == RPKT_S_OK &&
+                                proto == 17u && l4 + 8u <= toff);
+    const bool nest = l4 >= l3 && (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u)) &&
+                      toff + (gre ? 4u : 8u) <= ioff && ioff <= in.l3;
+    const bool ok = carrier && (v6 || det == 0x0800u) && (v6 || (frag & 0x3fffu) == 0u) && nest;
+    return TunWhere{ok, v6, !gre, gtp, l3, l4, toff, ioff, pdst};
+}
+
+// Plan words 8..11 (q[0..3]) and the tunnel bits of word 7 for a frame whose inner frame `s` is
+// cut; false when the GRE header forbids it (the S or R bit, or C without room for its word).
+template <class Header>
+__device__ __forceinline__ bool tunnel_constants(const Header& H, const L4Where& s,
+                                                 const TunWhere& w, uint32_t (&q)[4],
+                                                 uint32_t& bits) {
+    const uint32_t l3 = w.l3, l4 = w.l4, toff = w.toff, po = s.po;
+    bool csum;
+    uint32_t origin, c = 0;
+    if (w.udp) {
+        csum = (H.dw(l4 + 4u) >> 16) != 0u;                      // a zero checksum stays zero
+        origin = l4;
+        if (csum) {
+            if (!w.v6) {
+                c = 17u + H.sum(l3 + 12u, l3 + 20u);
+            } else {
+                const uint32_t pd = ip6_pseudo_dst(w.pdst, l3, l4);
+                c = 17u + H.sum(l3 + 8u, l3 + 24u) + H.sum(pd, pd + 16u);
+            }
+        }
+    } else {
+        const uint32_t g0 = H.dw(toff) & 0xffu;                  // C 0x80, R 0x40, K 0x20, S 0x10
+        csum = (g0 & 0x80u) != 0u;
+        if ((g0 & 0x50u) || (csum && toff + 8u > w.ioff)) return false;
+        origin = toff;
+    }
+    if (csum) {
+        // [origin, po) without the bytes the write patches: each leaves by its complement
+        c += H.sum(origin, po);
+        auto drop = [&](uint32_t off, uint32_t n) {
+            const uint32_t v = H.sum(off, off + n);
+            c += 0xffffu ^ (((off - origin) & 1u) ? bswap16(v) : v);
+        };
+        if (w.udp) drop(l4 + 4u, 4u); else drop(toff + 4u, 2u);
+        if (w.gtp) drop(toff + 2u, 2u);
+        if (s.v6) {
+            drop(s.l3 + 4u, 2u);
+        } else {
+            drop(s.l3 + 2u, 4u);
+            drop(s.l3 + 10u, 2u);
+        }
+        drop(s.l4 + 4u, 4u);
+        if (!s.udp) {
+            drop(s.l4 + 13u, 1u);
+            drop(s.l4 + 16u, 2u);
+        }
+    }
+    uint32_t opc = 0, oident = 0;
+    if (!w.v6) {
+        const uint32_t ip0 = H.dw(l3), ip1 = H.dw(l3 + 4u), ip2 = H.dw(l3 + 8u);
+        oident = be16_lo(ip1);
+        opc = H.sum(l3, l4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ oident) + (0xffffu ^ be16_hi(ip2));
+    }
+    q[0] = l3 | (l4 << 16);
+    q[1] = toff;
+    q[2] = fold16(opc) | (oident << 16);
+    q[3] = fold16(c);
+    bits = kTunOn | (w.v6 ? kTunV6 : 0u) | (w.udp ? kTunUdp : 0u) | (w.gtp ? kTunGtp : 0u) |
+           (csum ? kTunCsum : 0u);
+    return true;
+}
+
+template <bool kUdp>
+__global__ __launch_bounds__(kSegBlock)
+void segment_tunnel_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
+                                const uint32_t* __restrict__ offsets, uint32_t stride,
+                                uint32_t frame_len, uint32_t n, const rpkt_rec_t* __restrict__ outer,
+                                const rpkt_tun_t* __restrict__ tun, const rpkt_rec_t* __restrict__ inner,
+                                uint32_t mss, u32x4* __restrict__ plan,
+                                uint32_t* __restrict__ seg_first, uint64_t* __restrict__ obase,
+                                uint64_t* __restrict__ part) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    uint64_t cnt = 0, bytes = 0;
+    uint32_t p[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, q[4] = {0u, 0u, 0u, 0u};
+
+    if (p0 < n) {                                                 // wave-uniform
+        // the tile's outer records through the stage, then its inner records through the same
+        uint32_t* st = stage[wave];
+        const uint32_t* w = st + lane * 21;
+        stage_records_tile(st, outer, p0, n, lane);
+        const uint32_t o0 = w[0], o5 = w[5], o7 = w[7], o8 = w[8], o16 = w[16], o17 = w[17];
+        wave_sync();
+        stage_records_tile(st, inner, p0, n, lane);
+        const u32x4 t = valid ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tun) + i)
+                              : u32x4{0u, 0u, 0u, 0u};
+        const Frame fr = valid ? frame_span(offsets, stride, frame_len, fb, i) : Frame{0u, 0u};
+        // no tunnel: the frame itself under its outer record; a decoded one: its inner frame
+        const bool tunnel = (t.x & 0xffu) != RPKT_TUN_NONE;
+        L4Where s = l4_where(o0, o5, o7, o8, o16, o17, fr.len, kUdp);
+        TunWhere tw{};
+        if (tunnel) {
+            s = l4_where(w, fr.len, kUdp);
+            tw = tun_where(o0, o5, o7, o8, o16, t, s);
+            s.on = s.on && ((t.x >> 8) & 0xffu) == RPKT_T_OK && tw.ok;
+        }
+        p[0] = fr.off;
+        p[1] = fr.len;
+        if (valid) {
+            cnt = 1;
+            bytes = fr.len;
+        }
+        if (valid && s.on && s.pl > mss) {
+            const FlatHeader H{make_rsrc(frames, fb), fb, fr.off};
+            uint32_t bits = 0;
+            if (!tunnel || tunnel_constants(H, s, tw, q, bits)) {  // segmented
+                cnt = (s.pl + mss - 1u) / mss;
+                bytes = cnt * s.po + s.pl;
+                seg_constants(H, s, p);
+                p[7] |= bits;
+            }
+        }
+    }
+    if (valid) {
+        plan[4 * (size_t)i + 2] = u32x4{q[0], q[1], q[2], q[3]};
+        plan[4 * (size_t)i + 3] = u32x4{0u, 0u, 0u, 0u};
+    }
+    plan_store<4>(valid, i, p, cnt, bytes, plan, seg_first, obase, part, red);
+}
+
+// The outer headers' patches of output k, P[5..8], after the inner ones P[0..4]; pc: plan
+// words 8..11, `pay` the payload's big-endian sum.
+__device__ __forceinline__ void tunnel_patches(const SegOut& o, u32x4 pb, u32x4 pc, uint32_t k,
+                                               uint32_t pay, SegPatch (&P)[kTunPatches]) {
+    P[5] = P[6] = P[7] = P[8] = SegPatch{0u, 0u, 0u};
+    if (!(pb.w & kTunOn)) return;                                 // wave-uniform
+    const uint32_t l3 = pc.x & 0xffffu, l4 = pc.x >> 16, toff = pc.y & 0xffffu;
+    const uint32_t tot = o.po + o.pk;
+    if (!(pb.w & kTunV6)) {
+        const uint32_t tlen = (tot - l3) & 0xffffu, ident = ((pc.z >> 16) + k) & 0xffffu;
+        const uint32_t ck = ~fold16((pc.z & 0xffffu) + tlen + ident) & 0xffffu;
+        P[5] = SegPatch{l3 + 2u, 4u, bswap16(tlen) | (bswap16(ident) << 16)};
+        P[6] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
+    } else {
+        P[5] = SegPatch{l3 + 4u, 2u, bswap16((tot - l3 - 40u) & 0xffffu)};
+    }
+    if (pb.w & kTunGtp) P[7] = SegPatch{toff + 2u, 2u, bswap16((tot - toff - 8u) & 0xffffu)};
+    const bool udp = (pb.w & kTunUdp) != 0u, csum = (pb.w & kTunCsum) != 0u;
+    const uint32_t origin = udp ? l4 : toff;
+    uint32_t sum = 0;
+    if (csum) {
+        sum = pc.w + (((o.po - origin) & 1u) ? bswap16(pay) : pay);
+        // the inner patches and the GTP-U length lie under the outer checksum
+        const int under[6] = {0, 1, 2, 3, 4, 7};
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+            const SegPatch& x = P[under[u]];
+            const uint32_t v = x.n >= 4u ? x.val : x.val & ((1u << (8u * x.n)) - 1u);
+            sum += be_sum((v & 0xffffu) + (v >> 16), x.off - origin);
+        }
+    }
+    if (udp) {
+        // the length is in the pseudo header and in the header
+        const uint32_t ulen = (tot - l4) & 0xffffu;
+        const uint32_t uck = csum ? udp_csum_field(sum + 2u * ulen) : 0u;
+        P[8] = SegPatch{l4 + 4u, 4u, bswap16(ulen) | (bswap16(uck) << 16)};
+    } else if (csum) {
+        P[8] = SegPatch{toff + 4u, 2u, bswap16(~fold16(sum) & 0xffffu)};   // RFC 2784: 0 stays 0
+    }
+}
+
+// write_output for the 64-B plan (pa, pb, pc)
+template <bool kUdp>
+__device__ __forceinline__ void write_tunnel_output(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                    __amdgpu_buffer_rsrc_t ro,
+                                                    uint32_t* __restrict__ out_offsets,
+                                                    uint32_t mss, uint32_t j, uint32_t k, u32x4 pa,
+                                                    u32x4 pb, u32x4 pc, uint32_t base, int lane) {
+    const uint32_t foff = pa.x, flen = pa.y;
+    if (!(pb.w & kSegOn)) {                                       // pass-through: a byte copy
+        if (lane == 0) out_offsets[j + 1] = base + flen;
+        wave_copy<false>(rs, fb, ro, foff, base, flen, lane);
+        return;
+    }
+    const SegOut o = seg_out(pa, pb, mss, k, base);
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.po + o.pk;
+    const uint32_t hfirst = header_dword(rs, fb, foff, o.d0, (uint32_t)lane);
+    const uint32_t part = wave_copy<true>(rs, fb, ro, foff + o.po + o.done, o.d0 + o.po, o.pk, lane);
+    const uint32_t pay = be_sum(wave_sum(fold16(part)), o.d0 + o.po);
+    SegPatch Pi[kSegPatches], P[kTunPatches];
+    seg_patches<kUdp>(o, pb, k, pay, Pi);
+#pragma unroll
+    for (int u = 0; u < kSegPatches; ++u) P[u] = Pi[u];
+    tunnel_patches(o, pb, pc, k, pay, P);
+    wave_copy_header(rs, fb, ro, foff, o.d0, o.po, hfirst, P, lane);
+}
+
+template <bool kUdp>
+__global__ __launch_bounds__(kSegBlock)
+void segment_tunnel_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
+                                 uint32_t mss, const u32x4* __restrict__ plan,
+                                 const uint32_t* __restrict__ seg_first,
+                                 const uint64_t* __restrict__ obase,
+                                 const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
+                                 uint32_t out_bytes, uint32_t* __restrict__ out_offsets,
+                                 uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t j0, jend, i;
+    if (!output_run(n, seg_first, totals, out_bytes, out_offsets, out_cap, lane, j0, jend, i)) return;
+    uint32_t cur = seg_first[i], nxt = seg_first[i + 1];
+    u32x4 pa = plan[4 * (size_t)i], pb = plan[4 * (size_t)i + 1], pc = plan[4 * (size_t)i + 2];
+    uint32_t base = (uint32_t)obase[i];                           // < need <= out_bytes < 4 GiB
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t j = j0; j < jend; ++j) {
+        if (j >= nxt) {                                           // the next frame's first output
+            while (j >= nxt && i + 1u < n) {
+                ++i;
+                cur = nxt;
+                nxt = seg_first[i + 1];
+            }
+            pa = plan[4 * (size_t)i];
+            pb = plan[4 * (size_t)i + 1];
+            pc = plan[4 * (size_t)i + 2];
+            base = (uint32_t)obase[i];
+        }
+        write_tunnel_output<kUdp>(rs, fb, ro, out_offsets, mss, j, j - cur, pa, pb, pc, base, lane);
+    }
+}
+
 // the scans and the write's grid, the same for both entries: `n` inputs planned into ws
 template <typename... KArgs, typename... Args>
 int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, uint32_t out_cap,
@@ -650,6 +927,31 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* c, const rpkt_rec_t* recs_dev, 
                           (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, n, mss, ws.plan,
                           seg_first_dev, ws.obase, totals_dev, out_frames_dev, (uint32_t)out_bytes,
                           out_offsets_dev, out_cap);
+}
+
+size_t rpkt_gpu_segment_tunnel_workspace_bytes(uint32_t n) { return seg_ws(nullptr, n, 4).bytes; }
+
+int rpkt_gpu_segment_tunnel_batch(const rpkt_batch_t* b, const rpkt_rec_t* outer_dev,
+                                  const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                  uint32_t mss, uint32_t flags, uint8_t* out_frames_dev,
+                                  uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
+                                  uint32_t* seg_first_dev, uint64_t* totals_dev, void* workspace_dev,
+                                  void* stream) {
+    RPKT_TRY(reframe_args_ok(b, outer_dev, mss, flags, RPKT_SEGMENT_UDP, out_frames_dev, out_bytes,
+                             out_offsets_dev, out_cap, seg_first_dev, totals_dev, workspace_dev,
+                             tun_dev, inner_dev));
+    if (b->n == 0) return RPKT_OK;
+
+    const SegWs ws = seg_ws(workspace_dev, b->n, 4);
+    const bool udp = (flags & RPKT_SEGMENT_UDP) != 0u;
+    RPKT_TRY(launch_batch(udp ? segment_tunnel_plan_kernel<true> : segment_tunnel_plan_kernel<false>,
+                          kSegBlock, 0, stream, *b, outer_dev, tun_dev, inner_dev, mss, ws.plan,
+                          seg_first_dev, ws.obase, ws.part));
+    return scan_and_write(udp ? segment_tunnel_write_kernel<true> : segment_tunnel_write_kernel<false>,
+                          ws, b->n, out_cap, seg_first_dev, totals_dev, (hipStream_t)stream,
+                          b->frames_dev, (uint32_t)b->frames_bytes, b->n, mss, ws.plan, seg_first_dev,
+                          ws.obase, totals_dev, out_frames_dev, (uint32_t)out_bytes, out_offsets_dev,
+                          out_cap);
 }
 
 }  // extern "C"

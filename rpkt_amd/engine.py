@@ -86,6 +86,9 @@ ABI = {
     "rpkt_gpu_segment_chains_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_segment_chains": (_i, [_C, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
                                      _p]),
+    "rpkt_gpu_segment_tunnel_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_segment_tunnel_batch": (_i, [_B, _p, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32,
+                                           _p, _p, _p, _p]),
     "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p, _p]),
@@ -682,6 +685,41 @@ def segment_chains(chains, recs, mss, out_frames=None, out_offsets=None, out_cap
     return _segment("rpkt_gpu_segment_chains", chains, "segment_chains", recs, mss, out_frames,
                     out_offsets, out_cap, out_bytes, seg_first, totals, workspace, stream, header_max,
                     udp)
+
+
+def segment_tunnel_workspace(n, device="cuda"):
+    """The workspace tensor of segment_tunnel_batch for n input frames
+    (rpkt_gpu_segment_tunnel_workspace_bytes)."""
+    return _workspace("segment_tunnel", n, device)
+
+
+def segment_tunnel_batch(batch, outer, tun, inner, mss, out_frames=None, out_offsets=None,
+                         out_cap=None, out_bytes=None, seg_first=None, totals=None, workspace=None,
+                         stream=None, header_max=None, udp=False):
+    """rpkt_gpu_segment_tunnel_batch: segmentation of the inner TCP (with udp=True,
+    RPKT_SEGMENT_UDP, also the inner UDP) of the VXLAN / GTP-U / GRE frames of `batch` at `mss`,
+    with the outer lengths and checksums fixed up; `outer`, `tun`, `inner` are
+    parse_tunnel_batch's three tensors for this batch.  A frame without a tunnel is cut as
+    segment_batch cuts it with its outer record.  The same return value as segment_batch:
+    (out, seg_first, totals).  The default sizes are segment_batch's with header_max, the longest
+    inner payload_off of the batch, 272 unless given: an outer Ethernet frame with two tags (22),
+    a 60-B outer IPv4 header (a plain outer IPv6 header is 40), UDP (8), a 12-B GTP-U header with
+    32 bytes of extension headers (VXLAN's 8 and GRE's 4..16 are shorter) and the 134 bytes
+    segment_batch allows for the inner frame: 268, rounded up to 16; give it for outer IPv6
+    extension headers or longer GTP-U extension chains."""
+    n, fbytes = batch.n, batch.frames.numel()
+    out_frames, out_bytes, out_offsets, out_cap, seg_first, totals, workspace = _reframe_outputs(
+        "segment_tunnel_batch", batch, outer, lambda: n + fbytes // mss,
+        lambda cap: fbytes + (cap - n) * (272 if header_max is None else header_max),
+        out_frames, out_offsets, out_cap, out_bytes, seg_first, "seg_first", totals, workspace,
+        "segment_tunnel")
+    if tun.numel() != n * 16 or inner.numel() != n * REC_BYTES:
+        raise RpktError("segment_tunnel_batch: tunnel or inner records do not fit %d frames" % n)
+    _call("rpkt_gpu_segment_tunnel_batch", ctypes.byref(batch.desc()), outer.data_ptr(),
+          tun.data_ptr(), inner.data_ptr(), mss, SEGMENT_UDP if udp else 0, out_frames.data_ptr(),
+          out_bytes, out_offsets.data_ptr(), out_cap, seg_first.data_ptr(), totals.data_ptr(),
+          workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
 
 
 COALESCE_TRUST_SUMS = 1

@@ -20,7 +20,8 @@ RPKT_SEGMENT_UDP, against tests/udp_reframe_model.py on the flattened chains (th
 parse's records, or the flat oracle's of the flattened bytes, which gather headers across the
 cuts), a generator batch through rpkt_gpu_segment_batch and its output through
 rpkt_gpu_coalesce_batch with random flags (RPKT_SEGMENT_UDP, RPKT_COALESCE_UDP, TRUST_SUMS)
-against the same model, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
+against the same model, a tunnel batch (config 13 / 14) through rpkt_gpu_segment_tunnel_batch at a
+random mss and flag against tests/segment_tunnel_model.py, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
 random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py; (d)
 a nested tunnel batch (tests/nested_tunnel_ref.py's recipe: config 13 / 14 frames, frame k
 wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level passes
@@ -47,6 +48,7 @@ import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
 import segment_chains_model  # noqa: E402
 import segment_model  # noqa: E402
+import segment_tunnel_model  # noqa: E402
 import tunnel_chain_model  # noqa: E402
 import tunnel_frames  # noqa: E402
 import udp_reframe_model  # noqa: E402
@@ -271,6 +273,26 @@ def check_segment_coalesce(rng, seed):
             "max_payload": max_payload, "n_seg": int(totals[0]), "n_out": int(ctot[0])}
 
 
+def check_segment_tunnel(rng, seed):
+    """rpkt_gpu_segment_tunnel_batch on a config 13 / 14 batch at a random mss, with or without
+    RPKT_SEGMENT_UDP, against tests/segment_tunnel_model.py."""
+    cfg = int(rng.choice([13, 14]))
+    hb = gen.make_batch(cfg, n=int(rng.integers(1, 3000)), seed=seed)
+    mss = int(rng.choice([7, 16, 17, 100, 300, 536, 1448, 65535]))
+    udp = bool(rng.random() < 0.5)
+    outer, tun, inner = segment_tunnel_model.tunnel_records(hb)
+    out, first, totals = segment_tunnel_model.segment(hb, outer, tun, inner, mss, udp)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    db = engine.DeviceBatch.from_host(hb)
+    odb, gs, gt = engine.segment_tunnel_batch(db, *engine.parse_tunnel_batch(db, segment_model.F6), mss,
+                                              out_cap=out_cap,
+                                              out_bytes=int(totals[1]) + int(rng.integers(0, 40)), udp=udp)
+    same_reframed("segment_tunnel_batch", odb, gs, gt, out, first, totals, out_cap)
+    kinds = segment_tunnel_model.cut_kinds(first, tun)
+    return {"cfg": cfg, "n": int(hb.n), "mss": mss, "udp": udp, "n_out": int(totals[0]),
+            "cut": [kinds[k] for k in (0, 1, 2, 3)]}
+
+
 def check_tunnel_chains(rng, seed):
     """rpkt_gpu_parse_tunnel_chains (records and flow events) against the model."""
     if rng.random() < 0.7:
@@ -344,6 +366,8 @@ def main():
                 rec["segment_chains"] = check_segment_chains(rng, seed)
                 step = "segment_coalesce"
                 rec["segment_coalesce"] = check_segment_coalesce(rng, seed)
+                step = "segment_tunnel"
+                rec["segment_tunnel"] = check_segment_tunnel(rng, seed)
                 step = "tunnel_chains"
                 rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
                 step = "tunnel_next"

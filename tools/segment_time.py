@@ -36,7 +36,18 @@ flat batch's, byte for byte.
 adds the same workload as UDP datagrams (a 42-byte header, 32,768 B of payload, mss 1448) cut
 with RPKT_SEGMENT_UDP, in the same interleaved rounds as the TCP leg (flags 0) and the device
 copy: `udp_over_tcp_per_byte` and `udp_over_copy_per_byte` are same-run ratios.  Its output is
-checked the same way: 23 segments a datagram, every one OK with valid IPv4 and UDP sums."""
+checked the same way: 23 segments a datagram, every one OK with valid IPv4 and UDP sums.
+
+    python tools/segment_time.py --tunnel [--out profiles/segment/tunnel_times.json]
+
+adds rpkt_gpu_segment_tunnel_batch on the same inner super-frames behind 50 bytes of outer
+Ether / IPv4 / UDP / VXLAN (the outer UDP checksum field not 0, so every output's is filled),
+located by a tunnel parse, in the same interleaved rounds as the TCP leg on the un-tunnelled
+inner frames and the device copy: `tunnel_over_tcp_per_output_byte` (the times over the output
+frame bytes), `tunnel_over_tcp_per_byte` and `tunnel_over_copy_per_byte` (over the bytes
+moved) are same-run ratios.  Its output is checked by a tunnel parse with both sums: 23
+segments a frame, every one decoded with valid outer and inner IPv4, UDP and TCP sums.  With
+--trace-launches the traced calls are the tunnel entry's."""
 import argparse
 import json
 import os
@@ -97,6 +108,26 @@ def udp_super_frames(n, seed):
     return f
 
 
+TUN_HDR = 50
+
+
+def vxlan_prefix():
+    """The 50 bytes in front of an inner super-frame: Ether / IPv4 / UDP 4789 / VXLAN (the UDP
+    checksum a non-zero placeholder: segmentation fills it whatever it holds)."""
+    p = np.zeros(TUN_HDR, dtype=np.uint8)
+    p[0:12] = (2, 0, 0, 0, 9, 1, 2, 0, 0, 0, 9, 2)
+    p[12:14] = (8, 0)
+    tot = 36 + HDR + PAYLOAD
+    p[14:24] = (0x45, 0, tot >> 8, tot & 255, 0x43, 0x21, 0x40, 0, 64, 17)
+    p[26:34] = (172, 16, 0, 1, 172, 16, 0, 2)
+    ck = rfc1071(p[14:34])
+    p[24:26] = (ck >> 8, ck & 255)
+    ulen = 16 + HDR + PAYLOAD
+    p[34:42] = (0xc0, 0x00, 0x12, 0xb5, ulen >> 8, ulen & 255, 0xbe, 0xef)
+    p[42:50] = (0x08, 0, 0, 0, 0x12, 0x34, 0x56, 0)
+    return p
+
+
 ROOM, HEADROOM = 2048, 128                                        # gen.MBUF_ROOM, MBUF_HEADROOM
 
 
@@ -152,13 +183,16 @@ def main():
                     help="also time rpkt_gpu_segment_chains on the same frames as mbuf chains")
     ap.add_argument("--udp", action="store_true",
                     help="also time RPKT_SEGMENT_UDP on the same workload as UDP datagrams")
+    ap.add_argument("--tunnel", action="store_true",
+                    help="also time rpkt_gpu_segment_tunnel_batch on the same frames behind VXLAN")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace pass")
     a = ap.parse_args()
-    a.out = a.out or ("profiles/udp_reframe/segment_times.json" if a.udp else
+    a.out = a.out or ("profiles/segment/tunnel_times.json" if a.tunnel else
+                      "profiles/udp_reframe/segment_times.json" if a.udp else
                       "profiles/segment_chains/times.json" if a.chains else "profiles/segment/times.json")
     import torch
     from rpkt_amd import engine
@@ -221,9 +255,28 @@ def main():
                                  workspace=ws, stream=stream, udp=True)
 
         legs = {"segment_udp": segment_udp, **legs}
+    if a.tunnel:
+        tlen = TUN_HDR + flen
+        tneed = n * (per * (TUN_HDR + HDR) + PAYLOAD)
+        prefix = torch.from_numpy(vxlan_prefix()).to("cuda")
+        tdbs = [engine.DeviceBatch(torch.cat([prefix.expand(n, TUN_HDR), db.frames.view(n, flen)],
+                                             dim=1).reshape(-1).contiguous(), n, stride=tlen)
+                for db in dbs]
+        trecs = [engine.parse_tunnel_batch(db, 0) for db in tdbs]
+        tun_out = torch.empty(tneed, dtype=torch.uint8, device="cuda")
+        tun_offsets, tun_first = torch.empty_like(out_offsets), torch.empty_like(seg_first)
+        tun_totals = torch.zeros_like(totals)
+        tws = engine.segment_tunnel_workspace(n)
+
+        def segment_tunnel(k):
+            engine.segment_tunnel_batch(tdbs[k % R], *trecs[k % R], MSS, out_frames=tun_out,
+                                        out_offsets=tun_offsets, seg_first=tun_first,
+                                        totals=tun_totals, workspace=tws, stream=stream)
+
+        legs = {"segment_tunnel": segment_tunnel, **legs}
     if a.trace_launches:
         for k in range(a.trace_launches):
-            (segment_chains if a.chains else segment)(k)
+            (segment_tunnel if a.tunnel else segment_chains if a.chains else segment)(k)
         torch.cuda.synchronize()
         return
     med, ms = time_legs(torch, stream, legs, a.launches, a.rounds)
@@ -258,6 +311,21 @@ def main():
         assert (urec["ip_sum"] == 0xffff).all() and (urec["l4_sum"] == 0xffff).all()
         assert (urec["payload_len"][~last] == MSS).all()
         assert (urec["payload_len"][last] == PAYLOAD - (per - 1) * MSS).all()
+
+    if a.tunnel:                                                  # the tunnel workload is what it claims
+        from rpkt_amd.records import as_tunnels
+        segment_tunnel(0)
+        torch.cuda.synchronize()
+        assert tun_totals.cpu().tolist() == [n_out, tneed], tun_totals.cpu().tolist()
+        assert torch.equal(tun_first, seg_first)
+        to, tt, ti = engine.parse_tunnel_batch(engine.DeviceBatch(tun_out, n_out, tun_offsets), 3)
+        to, tt, ti = as_records(to.cpu().numpy()), as_tunnels(tt.cpu().numpy()), as_records(ti.cpu().numpy())
+        assert (tt["kind"] == 1).all() and (tt["status"] == 0).all()
+        assert (to["status"] == 0).all() and (ti["status"] == 0).all()
+        assert (to["ip_sum"] == 0xffff).all() and (to["l4_sum"] == 0xffff).all()
+        assert (ti["ip_sum"] == 0xffff).all() and (ti["l4_sum"] == 0xffff).all()
+        assert (ti["payload_len"][~last] == MSS).all()
+        assert (ti["payload_len"][last] == PAYLOAD - (per - 1) * MSS).all()
 
     moved = {"frames_in": n * flen, "records_in": n * 80, "frames_out": need,
              "offsets_out": (n_out + 1) * 4}
@@ -295,6 +363,18 @@ def main():
         res["udp_over_tcp_per_byte"] = round((med["segment_udp"] / ualg) / (med["segment_batch"] / alg), 4)
         res["udp_over_copy_per_byte"] = round(
             (med["segment_udp"] / ualg) / (med["device_copy"] / (2 * n * flen)), 4)
+    if a.tunnel:
+        talg = n * tlen + n * (80 + 16 + 80) + tneed + (n_out + 1) * 4
+        res["tunnel"] = {"frame_len": tlen, "bytes": talg, "frames_out": tneed}
+        res["ms"]["segment_tunnel"]["bytes"] = talg
+        res["ms"]["segment_tunnel"]["fraction_of_8TBs"] = round(
+            talg / (med["segment_tunnel"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        res["tunnel_over_tcp_per_output_byte"] = round(
+            (med["segment_tunnel"] / tneed) / (med["segment_batch"] / need), 4)
+        res["tunnel_over_tcp_per_byte"] = round(
+            (med["segment_tunnel"] / talg) / (med["segment_batch"] / alg), 4)
+        res["tunnel_over_copy_per_byte"] = round(
+            (med["segment_tunnel"] / talg) / (med["device_copy"] / (2 * n * flen)), 4)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
