@@ -428,6 +428,20 @@ extern "C" {
                                    src_first_dev: *mut u32, out_mss_dev: *mut u16,
                                    totals_dev: *mut u64, workspace_dev: *mut c_void,
                                    stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_coalesce_tunnel_batch for n positions.
+    pub fn rpkt_gpu_coalesce_tunnel_workspace_bytes(n: u32) -> usize;
+    /// Receive coalescing of the inner TCP / UDP of VXLAN, GTP-U and GRE frames, the inverse
+    /// of rpkt_gpu_segment_tunnel_batch: `outer_dev`, `tun_dev`, `inner_dev` are the outputs of
+    /// rpkt_gpu_parse_tunnel_batch on this batch; everything else as rpkt_gpu_coalesce_batch.
+    pub fn rpkt_gpu_coalesce_tunnel_batch(batch: *const rpkt_batch_t,
+                                          outer_dev: *const rpkt_rec_t,
+                                          tun_dev: *const rpkt_tun_t,
+                                          inner_dev: *const rpkt_rec_t, order_dev: *const u32,
+                                          max_payload: u32, flags: u32, out_frames_dev: *mut u8,
+                                          out_bytes: u64, out_offsets_dev: *mut u32, out_cap: u32,
+                                          src_first_dev: *mut u32, out_mss_dev: *mut u16,
+                                          totals_dev: *mut u64, workspace_dev: *mut c_void,
+                                          stream: *mut c_void) -> c_int;
     pub fn rpkt_gpu_build_tunnel_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
                                        tun_dev: *const rpkt_tun_t, flags: u32, built_dev: *mut u8,
                                        stream: *mut c_void) -> c_int;

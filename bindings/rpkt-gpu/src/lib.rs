@@ -574,6 +574,33 @@ pub unsafe fn coalesce_batch_flags(batch: &ffi::rpkt_batch_t, recs_dev: *const R
                                        workspace_dev, stream))
 }
 
+/// rpkt_gpu_coalesce_tunnel_workspace_bytes: the workspace of coalesce_tunnel_batch for `n`
+/// positions.
+pub fn coalesce_tunnel_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_coalesce_tunnel_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_coalesce_tunnel_batch: receive coalescing (GRO) of the inner TCP (with
+/// `ffi::RPKT_COALESCE_UDP` in `flags` also the inner UDP) of VXLAN, GTP-U and GRE frames, the
+/// outer lengths and checksums repaired; a frame without a tunnel is merged as coalesce_batch
+/// merges it.  `flags`: any of `ffi::RPKT_COALESCE_TRUST_SUMS` and `ffi::RPKT_COALESCE_UDP`.
+///
+/// # Safety
+/// As for `coalesce_batch`, with `outer_dev`, `tun_dev` and `inner_dev` the three outputs of a
+/// tunnel parse of this same batch and `workspace_dev` holding
+/// `coalesce_tunnel_workspace_bytes(batch.n)` bytes (16-byte aligned).
+pub unsafe fn coalesce_tunnel_batch(batch: &ffi::rpkt_batch_t, outer_dev: *const Rec,
+                                    tun_dev: *const ffi::rpkt_tun_t, inner_dev: *const Rec,
+                                    order_dev: *const u32, max_payload: u32, flags: u32,
+                                    out: &CoalesceOut, workspace_dev: *mut core::ffi::c_void,
+                                    stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_coalesce_tunnel_batch(batch, outer_dev, tun_dev, inner_dev, order_dev,
+                                              max_payload, flags, out.frames_dev, out.out_bytes,
+                                              out.offsets_dev, out.out_cap, out.src_first_dev,
+                                              out.out_mss_dev, out.totals_dev, workspace_dev,
+                                              stream))
+}
+
 /// rpkt_gpu_parse_tunnel_next: the next tunnel level (nested tunnels) from the tunnel and
 /// inner records of the level before, without flow events.
 ///

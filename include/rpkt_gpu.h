@@ -117,7 +117,9 @@ enum rpkt_status {
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
- *     mss's place.
+ *     mss's place;
+ *   rpkt_gpu_coalesce_tunnel_batch: rpkt_gpu_coalesce_batch's order with outer_dev, tun_dev and
+ *     inner_dev in recs_dev's places: each required (E_INVAL) and 16-byte aligned (E_ALIGN).
  * Where an entry leaves that order (kept as it is, callers may rely on it):
  *   rpkt_gpu_parse_tunnel_batch and each slot of rpkt_gpu_parse_tunnel_ring test the flow
  *     events first, before n == 0: an empty batch with RPKT_F_FLOW_EV and no event buffer is
@@ -898,7 +900,8 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_
  * unspecified, but every load goes through the frames buffer resource and every store through
  * the output's, and offsets that do not nest as above make the frame pass through: wrong
  * frames, never a fault.
- * Not covered: coalescing of tunnelled frames, tunnel segmentation over mbuf chains, nested
+ * The inverse is rpkt_gpu_coalesce_tunnel_batch (below).
+ * Not covered: tunnel segmentation over mbuf chains, nested
  * tunnels (only the level-1 records are accepted: the inner frame of a second tunnel level is
  * payload here), a segment size per flow, GRE sequence numbers, turning a zero outer UDP
  * checksum into a filled one. */
@@ -994,8 +997,9 @@ int rpkt_gpu_segment_tunnel_batch(const rpkt_batch_t* batch, const rpkt_rec_t* o
  * parse -> coalesce captures as one graph.  Records from another batch give unspecified output
  * but never a fault: all loads go through the frames buffer resource and offsets that do not
  * nest make a frame ineligible.
- * Not covered: mbuf chains, the inner TCP or UDP of tunnelled frames, keeping an IPv4 "no
- * checksum" across a merge. */
+ * Not covered: mbuf chains, the inner TCP or UDP of tunnelled frames (to this entry a tunnelled
+ * frame is what its outer record says; rpkt_gpu_coalesce_tunnel_batch, below, merges the inner
+ * flow), keeping an IPv4 "no checksum" across a merge. */
 #define RPKT_COALESCE_TRUST_SUMS 1u   /* do not require valid sums in the records */
 #define RPKT_COALESCE_UDP 16u   /* also coalesce UDP datagrams */
 
@@ -1008,6 +1012,97 @@ int rpkt_gpu_coalesce_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_de
                             uint32_t* src_first_dev,        /* n + 1 entries */
                             uint16_t* out_mss_dev,          /* optional, n entries */
                             uint64_t* totals_dev, void* workspace_dev, void* stream);
+
+/* Coalescing of the inner TCP / UDP of tunnels: the receive side of a VTEP or UPF, the inverse
+ * of rpkt_gpu_segment_tunnel_batch.  To rpkt_gpu_coalesce_batch a tunnelled frame is an outer UDP
+ * datagram or a GRE packet; this entry merges the segments of the INNER flow and repairs every
+ * outer length and checksum, as Linux does in udp_gro_receive -> vxlan_gro_receive and in
+ * gre_gro_receive.  coalesce(segment(F)) == F for every frame the tunnel cut accepts.
+ *
+ * outer_dev, tun_dev, inner_dev: the three outputs of rpkt_gpu_parse_tunnel_batch on this same
+ * batch (level 1; RPKT_F_IPV6 for IPv6 at either level; RPKT_F_IP_SUM | RPKT_F_L4_SUM unless
+ * RPKT_COALESCE_TRUST_SUMS).  The records locate things and give the verdicts; every header byte
+ * is taken from the frame.  order_dev (entries >= n make empty positions; it need not be a
+ * permutation), max_payload 1..65535, flags (0 or any of RPKT_COALESCE_TRUST_SUMS and
+ * RPKT_COALESCE_UDP), the outputs, src_first_dev, out_mss_dev, totals_dev, the overflow
+ * behaviour, the spare offset slots, "nothing written outside the buffers" and "plan, prefix
+ * sums and write on `stream` with no host step" are rpkt_gpu_coalesce_batch's contract word for
+ * word.  Below O, T, I are position i's outer, tunnel and inner record; ipo = I.payload_off, p =
+ * I.payload_len clamped to the frame, tot = ipo + p, toff = T.tun_off, ioff = T.inner_off.
+ *
+ * ELIGIBLE:
+ *   No tunnel   T.kind == RPKT_TUN_NONE: the position is eligible, compared and merged exactly
+ *               as rpkt_gpu_coalesce_batch treats it with record O.  It never continues a
+ *               tunnelled position and a tunnelled position never continues it: a mixed receive
+ *               burst needs this one call only.
+ *   Undecoded   T.kind != NONE and T.status != RPKT_T_OK: never eligible, a byte copy.  Its
+ *               outer UDP is never merged, with or without RPKT_COALESCE_UDP.
+ *   Decoded     eligible iff all of these hold:
+ *               - inner: I is eligible under rpkt_gpu_coalesce_batch's TCP rule, or with
+ *                 RPKT_COALESCE_UDP its UDP rule (a zero inner UDP checksum is never merged);
+ *                 I's offsets are positions in the outer frame and nest within frame_len; the
+ *                 verdicts (status, ip_sum, l4_sum) are I's;
+ *               - carrier: what rpkt_gpu_segment_tunnel_batch asks of a frame it cuts: O IPv4 or
+ *                 IPv6 by its dispatch ethertype and no fragment, O.l3_off + 20 (IPv6: + 40) <=
+ *                 O.l4_off, an IPv4 header within 60 bytes; VXLAN / GTP-U: O.status ==
+ *                 RPKT_S_OK, ip_protocol 17, O.l4_off + 8 <= toff; GRE: ip_protocol 47, O.l4_off
+ *                 == toff; toff + 8 (GRE: + 4, with the C bit + 8) <= ioff <= I.l3_off; the GRE S
+ *                 and R bits clear;
+ *               - lengths agree, with or without TRUST_SUMS: every length field a merge rewrites
+ *                 says tot already: outer IPv4 packet_len == tot - O.l3_off or outer IPv6
+ *                 payload_len == tot - O.l3_off - 40; VXLAN / GTP-U: outer UDP length == tot -
+ *                 O.l4_off; GTP-U length == tot - toff - 8.  Bytes of the frame past tot (outer
+ *                 Ethernet padding) are allowed and not carried, as in the flat rule.  A frame
+ *                 with bytes between the inner packet's end and the outer packet's end (the
+ *                 padding of an inner Ethernet frame) is not merged: a merge would drop bytes a
+ *                 length field counts (Linux's inet_gro_receive flushes on the same mismatch);
+ *               - outer sums, without TRUST_SUMS: outer IPv4: O.ip_sum == 0xffff; VXLAN / GTP-U:
+ *                 the frame's outer UDP checksum field is 0, or O.l4_sum == 0xffff; GRE with C:
+ *                 O.l4_sum == 0xffff.
+ * B(i) for two decoded positions: both eligible; equal T.kind, outer IP version, inner IP
+ * version and L4 protocol; equal O.l3_off, O.l4_off, toff, ioff, I.l3_off, I.l4_off, ipo; header
+ * bytes [0, ipo) equal, ignoring only the inner bytes the flat rule ignores (relative to I's
+ * l3_off / l4_off), outer IPv4 bytes ol3+2..5 and ol3+10..11, outer IPv6 bytes ol3+4..5, outer
+ * UDP bytes ol4+4..7, GTP-U bytes toff+2..3 and GRE-with-C bytes toff+4..5; the two outer UDP
+ * checksum fields both 0 or both not 0 (Linux: !uh->check ^ !uh2->check); the flat rule's inner
+ * sequence, inner ident and FIN / PSH / CWR conditions; for outer IPv4 with DF clear ident_i ==
+ * ident_{i-1} + 1 (mod 2^16), with DF set the outer ident is ignored.  So outer MACs, tags,
+ * addresses, TOS / TTL and ports (VXLAN source-port entropy is per inner flow), VNI / TEID / key
+ * and every other tunnel header byte match, GTP-U sequence, N-PDU and extension headers
+ * included.
+ * short, link and the greedy cut are the flat rule's with p the inner payload length; a group's
+ * payload stays <= min(max_payload, 65535 - inner ip_hdrs, 65535 - (ipo - O.l3_off)) (outer
+ * IPv6: 65535 - (ipo - O.l3_off - 40)), so every 16-bit length field fits.
+ * A merged output: the head's bytes [0, ipo), then every member's [ipo, + p) in order; the inner
+ * headers as rpkt_gpu_coalesce_batch writes a merged frame's; the tunnel and outer headers as
+ * rpkt_gpu_segment_tunnel_batch writes them for segment 0 of a frame whose total is the merged
+ * one: the GTP-U length; the GRE checksum with C (0 stays 0); the outer UDP length; the outer
+ * UDP checksum (an input field of 0 stays 0 over IPv4 and IPv6, else filled, 0 written as
+ * 0xffff, the IPv6 pseudo destination under rpkt_gpu_build_batch's rule); the outer IPv4
+ * packet_len, the head's ident, the checksum refilled; the outer IPv6 payload_len.
+ * out_mss_dev[j] is the head's inner payload length.  A group of one is a byte copy of
+ * [0, frame_len).  rpkt_gpu_parse_tunnel_batch with RPKT_F_FLOW_EV keys its events by the inner
+ * flow, so a stable sort of their buckets is the order_dev of an interleaved burst.
+ * workspace_dev: rpkt_gpu_coalesce_tunnel_workspace_bytes(n) bytes, 16-byte aligned.
+ * Argument checks: rpkt_gpu_coalesce_batch's in its order, with tun_dev and inner_dev required
+ * and 16-byte aligned along with outer_dev, as in rpkt_gpu_segment_tunnel_batch.
+ * Records from another batch give unspecified frames but never a fault: every frame load goes
+ * through the frames buffer resource, every output store through the output's, and offsets
+ * that do not nest make a position ineligible.
+ * Not covered: mbuf chains, nested tunnels (only the level-1 records are accepted), a stream
+ * whose GTP-U sequence number runs on (the sequence bytes are compared, so it does not merge),
+ * GRE sequence numbers, turning a zero outer UDP checksum into a filled one, Linux's sequential
+ * state machine. */
+size_t rpkt_gpu_coalesce_tunnel_workspace_bytes(uint32_t n);
+int rpkt_gpu_coalesce_tunnel_batch(const rpkt_batch_t* batch, const rpkt_rec_t* outer_dev,
+                                   const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                   const uint32_t* order_dev,      /* optional, n entries */
+                                   uint32_t max_payload, uint32_t flags,
+                                   uint8_t* out_frames_dev, uint64_t out_bytes,
+                                   uint32_t* out_offsets_dev, uint32_t out_cap,
+                                   uint32_t* src_first_dev,        /* n + 1 entries */
+                                   uint16_t* out_mss_dev,          /* optional, n entries */
+                                   uint64_t* totals_dev, void* workspace_dev, void* stream);
 
 /* ---- Option iterators ----------------------------------------------------------- */
 

@@ -37,6 +37,11 @@
 // Every load of frame bytes goes through the frames buffer resource and every store of
 // output bytes through one over [out_frames_dev, + out_bytes); an overflowing call (totals
 // past the capacities) writes its totals, src_first and out_mss and nothing else.
+//
+// rpkt_gpu_coalesce_tunnel_batch (the inner TCP / UDP of VXLAN, GTP-U and GRE frames) is the
+// same eight launches with the inner record: a plan kernel of its own that also judges the
+// carrier and writes 16 B more per position, <kTun> instantiations of link, group and header,
+// and heads, sums, place and copy as they are; see "tunnels" below.
 #include "rpkt_segcopy.h"
 
 namespace {
@@ -50,9 +55,10 @@ struct CoWs {
     uint32_t* aux;
     uint64_t* part;
     uint32_t* pmax;
+    u32x4*    tplan;      // the tunnel entry's: 16 B more per position ("tunnels" below)
     size_t    bytes;
 };
-inline CoWs co_ws(void* ws, uint32_t n) {
+inline CoWs co_ws(void* ws, uint32_t n, bool tunnel = false) {
     Carve c(ws);
     CoWs w;
     w.plan = c.take<u32x4>(2 * (size_t)n);
@@ -60,6 +66,7 @@ inline CoWs co_ws(void* ws, uint32_t n) {
     w.aux = c.take<uint32_t>(n);
     w.part = c.take<uint64_t>(2 * (size_t)blocks(n));
     w.pmax = c.take<uint32_t>(blocks(n));
+    w.tplan = tunnel ? c.take<u32x4>(n) : nullptr;
     w.bytes = c.used();
     return w;
 }
@@ -77,6 +84,38 @@ constexpr uint32_t kCoLink = 1u << 16, kCoShort = 1u << 17;
 constexpr uint32_t kFin = 0x01u, kSyn = 0x02u, kRst = 0x04u, kPsh = 0x08u, kUrg = 0x20u, kCwr = 0x80u;
 
 // ---- 1. plan ---------------------------------------------------------------------------
+
+// What the header of a frame that may be eligible (`s`) adds to its plan: seq, ident | TCP byte
+// 13 << 16, kCoDF; ok: its flags (UDP: its checksum field) allow a merge.
+struct CoLook {
+    uint32_t seq, idfl, df;
+    bool ok;
+};
+__device__ __forceinline__ CoLook co_look(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t foff,
+                                          const L4Where& s) {
+    const uint32_t a3 = foff + s.l3, a4 = foff + s.l4;
+    // t1: TCP's seq, UDP's length and checksum; a UDP frame has no byte 13 (t3 is payload)
+    const uint32_t t1 = gdword(rs, fb, a4 + 4u), t3 = gdword(rs, fb, a4 + 12u);
+    const uint32_t tf = s.udp ? 0u : (t3 >> 8) & 0xffu;           // TCP byte 13
+    CoLook k{s.udp ? 0u : bswap32(t1), tf << 16, 0u, false};
+    if (!s.v6) {
+        const uint32_t ip1 = gdword(rs, fb, a3 + 4u);
+        k.idfl |= be16_lo(ip1);
+        k.df = (be16_hi(ip1) & 0x4000u) ? kCoDF : 0u;
+    }
+    // a UDP datagram sent without a checksum (field 0) is not merged, sums trusted or not
+    k.ok = s.udp ? be16_hi(t1) != 0u : (tf & (kSyn | kRst | kUrg)) == 0u;
+    return k;
+}
+
+// position i's plan words 0..7
+__device__ __forceinline__ void plan_store(u32x4* __restrict__ plan, uint32_t i, Frame fr,
+                                           const L4Where& s, bool elig, const CoLook& k) {
+    plan[2 * (size_t)i] = u32x4{fr.off, fr.len, elig ? s.l3 | (s.l4 << 16) : 0u,
+                                elig ? s.po | (s.pl << 16) : 0u};
+    const uint32_t bits = kCoElig | (s.v6 ? kCoV6 : 0u) | k.df | (s.udp ? kCoUdp : 0u);
+    plan[2 * (size_t)i + 1] = u32x4{k.seq, k.idfl, elig ? bits | (s.pdst << 16) : 0u, 0u};
+}
 
 // <kUdp>: the entry's RPKT_COALESCE_UDP.  The kernels that test the protocol (plan, link,
 // header) take it as a template argument, so a call without the flag launches the code
@@ -114,32 +153,134 @@ void coalesce_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
     const Frame fr = present ? frame_span(offsets, stride, frame_len, fb, f) : Frame{0u, 0u};
     // the frames segmentation cuts, with a payload and sums that verified
     const L4Where s = l4_where(w0, w5, w7, w8, w16, w17, fr.len, kUdp);
-    const bool v6 = s.v6;
-    const uint32_t l3 = s.l3, l4 = s.l4, po = s.po, pl = s.pl, pdst = s.pdst;
-    const bool sums = trust || ((w18 >> 16) == 0xffffu && (v6 || (w18 & 0xffffu) == 0xffffu));
-    bool elig = present && s.on && pl >= 1u && sums;
-    uint32_t seq = 0, idfl = 0, df = 0;
+    const bool sums = trust || ((w18 >> 16) == 0xffffu && (s.v6 || (w18 & 0xffffu) == 0xffffu));
+    bool elig = present && s.on && s.pl >= 1u && sums;
+    CoLook k{0u, 0u, 0u, false};
     if (elig) {
-        const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
-        const uint32_t a3 = fr.off + l3, a4 = fr.off + l4;
-        // t1: TCP's seq, UDP's length and checksum; a UDP frame has no byte 13 (t3 is payload)
-        const uint32_t t1 = gdword(rs, fb, a4 + 4u), t3 = gdword(rs, fb, a4 + 12u);
-        const uint32_t tf = s.udp ? 0u : (t3 >> 8) & 0xffu;       // TCP byte 13
-        seq = s.udp ? 0u : bswap32(t1);
-        idfl = tf << 16;
-        if (!v6) {
-            const uint32_t ip1 = gdword(rs, fb, a3 + 4u);
-            idfl |= be16_lo(ip1);
-            df = (be16_hi(ip1) & 0x4000u) ? kCoDF : 0u;
+        k = co_look(make_rsrc(frames, fb), fb, fr.off, s);
+        elig = k.ok;
+    }
+    if (valid) plan_store(plan, i, fr, s, elig, k);
+}
+
+// ---- tunnels: the inner TCP / UDP of VXLAN, GTP-U and GRE frames ------------------------
+//
+// rpkt_gpu_coalesce_tunnel_batch merges the inner frames of decoded tunnels: the inner
+// record's offsets are positions in the outer frame, so a tunnelled position's 32-B plan is
+// the flat one under the inner record -- group, place and copy do not know the difference --
+// and 16 B more per position (tplan) carry the carrier:
+//   x outer l3 | outer l4 << 16, y tun_off | inner_off << 16, z outer ident | outer
+//   ip6_pdst_off << 16, w kTunOn | kTunV6 | kTunUdp | kTunGtp | kTunCsum (the outer UDP
+//   checksum field is not 0; GRE: C) | kTunDF (all 0 unless an eligible tunnelled position).
+// The carrier rule is segmentation's (tun_where, rpkt_segcopy.h); the plan adds the length
+// fields that must agree and the outer sums, the link the outer bytes that may differ, the
+// outer ident and the zero / non-zero outer checksum, the group the outer IP's limit, the
+// header the outer patches (tunnel_constants and tunnel_patches, as segment 0 of a cut).
+// These take <kTun>: the flat entry launches the code without any of it.
+constexpr uint32_t kTunDF = 256u;
+
+template <bool kUdp>
+__global__ __launch_bounds__(kSegBlock)
+void coalesce_tunnel_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
+                                 const uint32_t* __restrict__ offsets, uint32_t stride,
+                                 uint32_t frame_len, uint32_t n, const rpkt_rec_t* __restrict__ outer,
+                                 const rpkt_tun_t* __restrict__ tun, const rpkt_rec_t* __restrict__ inner,
+                                 const uint32_t* __restrict__ order, uint32_t trust,
+                                 u32x4* __restrict__ plan, u32x4* __restrict__ tplan) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    if (p0 >= n) return;                                          // wave-uniform
+
+    uint32_t f = valid ? i : n;                                   // the position's frame
+    uint32_t o[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u}, in[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    u32x4 t = {0u, 0u, 0u, 0u};
+    const u32x4* tq = reinterpret_cast<const u32x4*>(tun);
+    if (!order) {
+        // the tile's outer records through the stage, then its inner records through the same
+        uint32_t* st = stage[wave];
+        const uint32_t* w = st + lane * 21;
+        stage_records_tile(st, outer, p0, n, lane);
+        o[0] = w[0], o[1] = w[5], o[2] = w[7], o[3] = w[8], o[4] = w[16], o[5] = w[17], o[6] = w[18];
+        wave_sync();
+        stage_records_tile(st, inner, p0, n, lane);
+        in[0] = w[0], in[1] = w[5], in[2] = w[7], in[3] = w[8], in[4] = w[16], in[5] = w[17], in[6] = w[18];
+        if (valid) t = __builtin_nontemporal_load(tq + i);
+    } else {
+        if (valid) f = order[i];
+        if (f < n) {                                              // an entry >= n: an empty frame
+            const u32x4* r = reinterpret_cast<const u32x4*>(outer + f);
+            const u32x4 q0 = r[0], q1 = r[1], q2 = r[2], q4 = r[4];
+            o[0] = q0.x, o[1] = q1.y, o[2] = q1.w, o[3] = q2.x, o[4] = q4.x, o[5] = q4.y, o[6] = q4.z;
+            t = tq[f];
+            if ((t.x & 0xffu) != RPKT_TUN_NONE) {
+                const u32x4* ri = reinterpret_cast<const u32x4*>(inner + f);
+                const u32x4 j0 = ri[0], j1 = ri[1], j2 = ri[2], j4 = ri[4];
+                in[0] = j0.x, in[1] = j1.y, in[2] = j1.w, in[3] = j2.x, in[4] = j4.x, in[5] = j4.y,
+                in[6] = j4.z;
+            }
         }
-        // a UDP datagram sent without a checksum (field 0) is not merged, sums trusted or not
-        elig = s.udp ? be16_hi(t1) != 0u : (tf & (kSyn | kRst | kUrg)) == 0u;
+    }
+    const bool present = f < n;
+    const Frame fr = present ? frame_span(offsets, stride, frame_len, fb, f) : Frame{0u, 0u};
+    // no tunnel: the frame itself under its outer record; a decoded one: its inner frame, with
+    // the inner record's verdicts
+    const bool tunnel = (t.x & 0xffu) != RPKT_TUN_NONE;
+    L4Where s = l4_where(o[0], o[1], o[2], o[3], o[4], o[5], fr.len, kUdp);
+    uint32_t w18 = o[6];
+    TunWhere tw{};
+    if (tunnel) {
+        s = l4_where(in[0], in[1], in[2], in[3], in[4], in[5], fr.len, kUdp);
+        tw = tun_where(o[0], o[1], o[2], o[3], o[4], t, s);
+        s.on = s.on && ((t.x >> 8) & 0xffu) == RPKT_T_OK && tw.ok;
+        w18 = in[6];
+    }
+    const bool sums = trust || ((w18 >> 16) == 0xffffu && (s.v6 || (w18 & 0xffffu) == 0xffffu));
+    bool elig = present && s.on && s.pl >= 1u && sums;
+    CoLook k{0u, 0u, 0u, false};
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    if (elig) {
+        k = co_look(rs, fb, fr.off, s);
+        elig = k.ok;
+    }
+    u32x4 pt = {0u, 0u, 0u, 0u};
+    if (elig && tunnel) {
+        // the length fields a merge rewrites say tot already; the GRE bits; the outer sums
+        const FlatHeader H{rs, fb, fr.off};
+        const uint32_t tot = s.po + s.pl;                         // >= every offset below: they nest
+        bool ok, csum;
+        if (tw.udp) {
+            const uint32_t u1 = H.dw(tw.l4 + 4u);
+            csum = be16_hi(u1) != 0u;
+            ok = be16_lo(u1) == tot - tw.l4;
+            if (tw.gtp) ok = ok && be16_hi(H.dw(tw.toff)) == tot - tw.toff - 8u;
+        } else {
+            const uint32_t g0 = H.dw(tw.toff) & 0xffu;            // C 0x80, R 0x40, K 0x20, S 0x10
+            csum = (g0 & 0x80u) != 0u;
+            ok = !(g0 & 0x50u) && !(csum && tw.toff + 8u > tw.ioff);
+        }
+        uint32_t oident = 0, odf = 0;
+        if (!tw.v6) {
+            const uint32_t ip0 = H.dw(tw.l3), ip1 = H.dw(tw.l3 + 4u);
+            ok = ok && be16_hi(ip0) == tot - tw.l3;
+            oident = be16_lo(ip1);
+            odf = (be16_hi(ip1) & 0x4000u) ? kTunDF : 0u;
+        } else {
+            ok = ok && be16_lo(H.dw(tw.l3 + 4u)) == tot - tw.l3 - 40u;
+        }
+        if (!trust)
+            ok = ok && (tw.v6 || (o[6] & 0xffffu) == 0xffffu) && (!csum || (o[6] >> 16) == 0xffffu);
+        elig = ok;
+        if (ok)
+            pt = u32x4{tw.l3 | (tw.l4 << 16), tw.toff | (tw.ioff << 16), oident | (tw.pdst << 16),
+                       kTunOn | (tw.v6 ? kTunV6 : 0u) | (tw.udp ? kTunUdp : 0u) |
+                           (tw.gtp ? kTunGtp : 0u) | (csum ? kTunCsum : 0u) | odf};
     }
     if (valid) {
-        plan[2 * (size_t)i] = u32x4{fr.off, fr.len, elig ? l3 | (l4 << 16) : 0u,
-                                    elig ? po | (pl << 16) : 0u};
-        const uint32_t bits = kCoElig | (v6 ? kCoV6 : 0u) | df | (s.udp ? kCoUdp : 0u);
-        plan[2 * (size_t)i + 1] = u32x4{seq, idfl, elig ? bits | (pdst << 16) : 0u, 0u};
+        plan_store(plan, i, fr, s, elig, k);
+        tplan[i] = pt;
     }
 }
 
@@ -165,6 +306,27 @@ __device__ __forceinline__ uint32_t header_keep(uint32_t x, uint32_t l3, uint32_
     return m;
 }
 
+// the same for the outer headers of a tunnelled position with tplan words `t`: the outer IP's
+// length, ident and checksum bytes, the outer UDP's length and checksum, the GTP-U length, the
+// GRE checksum.  They lie before the inner headers, so the two masks are ANDed.
+__device__ __forceinline__ uint32_t outer_keep(uint32_t x, u32x4 t) {
+    const uint32_t l3 = t.x & 0xffffu, l4 = t.x >> 16, toff = t.y & 0xffffu;
+    const bool v6 = (t.w & kTunV6) != 0u, udp = (t.w & kTunUdp) != 0u;
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; ++b) {
+        const uint32_t y = x + b, d3 = y - l3, d4 = y - l4, dt = y - toff;
+        uint32_t keep = 0xffu;
+        if (!v6 && ((d3 >= 2u && d3 <= 5u) || d3 == 10u || d3 == 11u)) keep = 0u;
+        else if (v6 && (d3 == 4u || d3 == 5u)) keep = 0u;
+        else if (udp && d4 >= 4u && d4 <= 7u) keep = 0u;
+        else if ((t.w & kTunGtp) && (dt == 2u || dt == 3u)) keep = 0u;
+        else if (!udp && (t.w & kTunCsum) && (dt == 4u || dt == 5u)) keep = 0u;
+        m |= keep << (8u * b);
+    }
+    return m;
+}
+
 // the frame-relative dwords of a header in turn: one aligned load a step
 struct HeaderWalk {
     uint32_t a4, sh, lo;
@@ -180,13 +342,26 @@ struct HeaderWalk {
 };
 
 // B(i), i >= 1: the frame at position i continues the one at i - 1
-template <bool kUdp>
+template <bool kUdp, bool kTun>
 __device__ __forceinline__ bool base_pred(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
-                                          const u32x4* __restrict__ plan, uint32_t i) {
+                                          const u32x4* __restrict__ plan,
+                                          const u32x4* __restrict__ tplan, uint32_t i) {
     const u32x4 pa = plan[2 * (size_t)i], pb = plan[2 * (size_t)i + 1];
     const u32x4 qa = plan[2 * (size_t)i - 2], qb = plan[2 * (size_t)i - 1];
     if (!(pb.z & qb.z & kCoElig) || ((pb.z ^ qb.z) & (kCoV6 | (kUdp ? kCoUdp : 0u))))
         return false;
+    u32x4 pt = {0u, 0u, 0u, 0u};
+    if (kTun) {
+        // a tunnelled position continues one in the same kind of tunnel over the same outer IP
+        // version at the same offsets, both outer checksums filled or both 0; the outer ident
+        pt = tplan[i];
+        const u32x4 qt = tplan[i - 1u];
+        if (((pt.w ^ qt.w) & (kTunOn | kTunV6 | kTunUdp | kTunGtp | kTunCsum)) || pt.x != qt.x ||
+            pt.y != qt.y)
+            return false;
+        if ((pt.w & kTunOn) && !(pt.w & (kTunV6 | kTunDF)) && ((pt.z ^ (qt.z + 1u)) & 0xffffu))
+            return false;
+    }
     if (pa.z != qa.z || ((pa.w ^ qa.w) & 0xffffu)) return false;          // l3, l4, payload_off
     const bool v6 = (pb.z & kCoV6) != 0u;
     // seq; UDP has no sequence and no flag condition (its flag words are 0)
@@ -195,8 +370,16 @@ __device__ __forceinline__ bool base_pred(__amdgpu_buffer_rsrc_t rs, uint32_t fb
     if (((qb.y >> 16) & (kFin | kPsh)) || ((pb.y >> 16) & kCwr)) return false;
     const uint32_t l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu;
     HeaderWalk a(rs, fb, pa.x), b(rs, fb, qa.x);
-    for (uint32_t x = 0; x < po; x += 4u)                                 // po <= 65535
-        if ((a.next(rs, fb) ^ b.next(rs, fb)) & header_keep(x, l3, l4, po, v6)) return false;
+    if constexpr (!kTun) {
+        for (uint32_t x = 0; x < po; x += 4u)                             // po <= 65535
+            if ((a.next(rs, fb) ^ b.next(rs, fb)) & header_keep(x, l3, l4, po, v6)) return false;
+    } else {
+        const bool outer = (pt.w & kTunOn) != 0u;
+        for (uint32_t x = 0; x < po; x += 4u) {
+            const uint32_t d = a.next(rs, fb) ^ b.next(rs, fb);
+            if (d & header_keep(x, l3, l4, po, v6) & (outer ? outer_keep(x, pt) : ~0u)) return false;
+        }
+    }
     return true;
 }
 
@@ -213,22 +396,23 @@ __device__ __forceinline__ uint32_t block_incl_max(uint32_t v, uint32_t* red) {
     return x;
 }
 
-template <bool kUdp>
+// tplan: the tunnel entry's (<kTun>), else unused
+template <bool kUdp, bool kTun>
 __global__ __launch_bounds__(kSegBlock)
 void coalesce_link_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
                           const u32x4* __restrict__ plan, uint32_t* __restrict__ aux,
-                          uint32_t* __restrict__ pmax) {
+                          uint32_t* __restrict__ pmax, const u32x4* __restrict__ tplan) {
     __shared__ uint32_t bs[kSegBlock];
     __shared__ uint32_t red[kWavesPerBlock];
     const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
     const bool valid = i < n;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
-    const bool bi = valid && i >= 1u && base_pred<kUdp>(rs, fb, plan, i);
+    const bool bi = valid && i >= 1u && base_pred<kUdp, kTun>(rs, fb, plan, tplan, i);
     bs[threadIdx.x] = bi ? 1u : 0u;
     __syncthreads();
     bool bp;                                                      // B(i - 1)
     if (threadIdx.x != 0u) bp = bs[threadIdx.x - 1u] != 0u;
-    else bp = valid && i >= 2u && base_pred<kUdp>(rs, fb, plan, i - 1u);
+    else bp = valid && i >= 2u && base_pred<kUdp, kTun>(rs, fb, plan, tplan, i - 1u);
     const uint32_t p = valid ? plan[2 * (size_t)i].w >> 16 : 0u;
     const uint32_t p1 = (valid && i >= 1u) ? plan[2 * (size_t)i - 2].w >> 16 : 0u;
     const uint32_t p2 = (valid && i >= 2u) ? plan[2 * (size_t)i - 4].w >> 16 : 0u;
@@ -262,10 +446,12 @@ void coalesce_scan_heads_kernel(uint32_t* __restrict__ pmax, uint32_t nb) {
 
 // ---- 4. group --------------------------------------------------------------------------
 
+template <bool kTun>
 __global__ __launch_bounds__(kSegBlock)
 void coalesce_group_kernel(uint32_t n, uint32_t max_payload, u32x4* __restrict__ plan,
                            const uint32_t* __restrict__ aux, const uint32_t* __restrict__ pmax,
-                           uint64_t* __restrict__ obase, uint64_t* __restrict__ part) {
+                           uint64_t* __restrict__ obase, uint64_t* __restrict__ part,
+                           const u32x4* __restrict__ tplan) {
     __shared__ uint64_t red[2 * kWavesPerBlock];
     const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
     uint64_t cnt = 0, bytes = 0;
@@ -281,7 +467,16 @@ void coalesce_group_kernel(uint32_t n, uint32_t max_payload, u32x4* __restrict__
         // a linked frame has its head's offsets and IP version
         const uint32_t iph = po - l3 - ((z & kCoV6) ? 40u : 0u);
         const uint32_t room = 65535u - (iph < 65535u ? iph : 65535u);
-        const uint32_t limit = max_payload < room ? max_payload : room;
+        uint32_t limit = max_payload < room ? max_payload : room;
+        if (kTun) {
+            // the outer IP's length field too (a linked frame has its head's outer offsets)
+            const u32x4 t = tplan[i];
+            if (t.w & kTunOn) {
+                const uint32_t oph = po - (t.x & 0xffffu) - ((t.w & kTunV6) ? 40u : 0u);
+                const uint32_t oroom = 65535u - (oph < 65535u ? oph : 65535u);
+                limit = limit < oroom ? limit : oroom;
+            }
+        }
         uint32_t K = ph ? limit / ph : 0u;
         if (K == 0u) K = 1u;
         const uint32_t r = i - h;
@@ -401,13 +596,13 @@ void coalesce_copy_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
 #endif
 constexpr uint32_t kCoHdrRun = RPKT_CO_HDR_RUN;
 
-template <bool kUdp>
+template <bool kUdp, bool kTun>
 __global__ __launch_bounds__(kSegBlock)
 void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
                             const u32x4* __restrict__ plan, const uint64_t* __restrict__ obase,
                             const uint32_t* __restrict__ aux, const uint32_t* __restrict__ src_first,
                             const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
-                            uint32_t out_bytes, uint32_t out_cap) {
+                            uint32_t out_bytes, uint32_t out_cap, const u32x4* __restrict__ tplan) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t j64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kCoHdrRun;
@@ -427,6 +622,9 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
         const uint32_t foff = pa.x, l3 = pa.z & 0xffffu, l4 = pa.z >> 16, po = pa.w & 0xffffu;
         const bool v6 = (pb.z & kCoV6) != 0u, udp = kUdp && (pb.z & kCoUdp);   // wave-uniform
         const uint32_t pdst = pb.z >> 16;
+        u32x4 pt = {0u, 0u, 0u, 0u};
+        if (kTun) pt = tplan[i0];
+        const bool tun = kTun && (pt.w & kTunOn);                         // wave-uniform
         const uint32_t P = end - d0 - po;                                 // the merged payload
         // the members' payload sums, all at the absolute destination phase
         uint32_t s = 0;
@@ -458,6 +656,17 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
                 x = range_be_sum(rs, fb, a3 + 8u, a3 + 24u) +
                     range_be_sum(rs, fb, foff + pd, foff + pd + 16u);
             }
+        } else if (kTun && lane == 3 && tun) {
+            // the outer constants of the head as segmentation plans them: x the outer IPv4 sum
+            // | ident << 16, y the outer checksum's sum without the patched bytes
+            const L4Where s{true, udp, v6, l3, l4, po, 0u, pdst};
+            const TunWhere w{true, (pt.w & kTunV6) != 0u, (pt.w & kTunUdp) != 0u,
+                             (pt.w & kTunGtp) != 0u, pt.x & 0xffffu, pt.x >> 16, pt.y & 0xffffu,
+                             pt.y >> 16, pt.z >> 16};
+            uint32_t q[4] = {0u, 0u, 0u, 0u}, bits = 0;
+            tunnel_constants(FlatHeader{rs, fb, foff}, s, w, q, bits);
+            x = q[2];
+            y = q[3];
         }
         const uint32_t ipc = (uint32_t)__builtin_amdgcn_readlane((int)x, 0);
         const uint32_t l4c = (uint32_t)__builtin_amdgcn_readlane((int)x, 1);
@@ -465,11 +674,15 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
         uint32_t w12 = (uint32_t)__builtin_amdgcn_readlane((int)y, 1);
         w12 |= lastf & (kFin | kPsh);
 
-        SegPatch Pt[kSegPatches];
+        // A tunnelled head (<kTun>): the outer patches follow the inner ones, which then cover
+        // every byte tunnel_constants takes out of the outer checksum's sum: the head's own
+        // ident and seq are written again.
+        SegPatch Pt[kTun ? kTunPatches : kSegPatches];
         if (!v6) {
             const uint32_t tot = po - l3 + P;
             const uint32_t ck = ~fold16(fold16(ipc) + tot) & 0xffffu;
             Pt[0] = SegPatch{l3 + 2u, 2u, bswap16(tot & 0xffffu)};
+            if (tun) Pt[0] = SegPatch{l3 + 2u, 4u, bswap16(tot & 0xffffu) | (bswap16(pb.y & 0xffffu) << 16)};
             Pt[1] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
         } else {
             Pt[0] = SegPatch{l3 + 4u, 2u, bswap16((po - l3 - 40u + P) & 0xffffu)};
@@ -487,9 +700,45 @@ void coalesce_header_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uin
             Pt[3] = SegPatch{l4 + 16u, 2u, bswap16(tck)};
         }
         Pt[4] = SegPatch{0u, 0u, 0u};
+        if constexpr (kTun) {
+            if (tun && !udp) Pt[4] = SegPatch{l4 + 4u, 4u, bswap32(pb.x)};
+            const uint32_t oq2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 3);
+            const uint32_t oq3 = (uint32_t)__builtin_amdgcn_readlane((int)y, 3);
+            const SegOut o{v6, true, l3, l4, po, 0u, P, d0};
+            tunnel_patches(o, u32x4{0u, 0u, 0u, pt.w}, u32x4{pt.x, pt.y, oq2, oq3}, 0u, pay, Pt);
+        }
         const uint32_t hfirst = header_dword(rs, fb, foff, d0, (uint32_t)lane);
         wave_copy_header(rs, fb, ro, foff, d0, po, hfirst, Pt, lane);
     }
+}
+
+// launches 2..8 for the `n` positions planned into ws (ws.tplan with <kTun>)
+template <bool kUdp, bool kTun>
+int link_and_write(const rpkt_batch_t* b, const CoWs& ws, uint32_t max_payload,
+                   uint8_t* out_frames_dev, uint64_t out_bytes, uint32_t* out_offsets_dev,
+                   uint32_t out_cap, uint32_t* src_first_dev, uint16_t* out_mss_dev,
+                   uint64_t* totals_dev, hipStream_t st) {
+    const uint32_t n = b->n, nb = blocks(n), fb = (uint32_t)b->frames_bytes;
+    const dim3 blk(kSegBlock), per(nb);
+    const u32x4* tplan = ws.tplan;
+    RPKT_TRY(launch(coalesce_link_kernel<kUdp, kTun>, per, blk, 0, st, b->frames_dev, fb, n, ws.plan,
+                    ws.aux, ws.pmax, tplan));
+    RPKT_TRY(launch(coalesce_scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
+    RPKT_TRY(launch(coalesce_group_kernel<kTun>, per, blk, 0, st, n, max_payload, ws.plan, ws.aux,
+                    ws.pmax, ws.obase, ws.part, tplan));
+    RPKT_TRY(launch(scan_parts_kernel, dim3(1), blk, 0, st, ws.part, nb, totals_dev,
+                    (uint32_t*)nullptr));
+    RPKT_TRY(launch(coalesce_place_kernel, per, blk, 0, st, n, ws.plan, ws.part, totals_dev, ws.obase,
+                    src_first_dev, out_mss_dev, out_offsets_dev, out_cap, (uint32_t)out_bytes));
+    const uint64_t cper = (uint64_t)kWavesPerBlock * kCoRun;             // positions a block
+    RPKT_TRY(launch(coalesce_copy_kernel, dim3((uint32_t)(((uint64_t)n + cper - 1) / cper)), blk, 0,
+                    st, b->frames_dev, fb, n, ws.plan, ws.obase, totals_dev, out_frames_dev,
+                    (uint32_t)out_bytes, out_cap, ws.aux));
+    const uint64_t hper = (uint64_t)kWavesPerBlock * kCoHdrRun;          // outputs a block
+    const uint32_t outs = n < out_cap ? n : out_cap;                     // n_out <= both, or overflow
+    return launch(coalesce_header_kernel<kUdp, kTun>, dim3((uint32_t)(((uint64_t)outs + hper - 1) / hper)),
+                  blk, 0, st, b->frames_dev, fb, n, ws.plan, ws.obase, ws.aux, src_first_dev,
+                  totals_dev, out_frames_dev, (uint32_t)out_bytes, out_cap, tplan);
 }
 
 }  // namespace
@@ -508,31 +757,38 @@ int rpkt_gpu_coalesce_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev,
                              out_offsets_dev, out_cap, src_first_dev, totals_dev, workspace_dev));
     if (b->n == 0) return RPKT_OK;
 
-    const uint32_t n = b->n, nb = blocks(n), fb = (uint32_t)b->frames_bytes;
-    const CoWs ws = co_ws(workspace_dev, n);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 blk(kSegBlock), per(nb);
+    const CoWs ws = co_ws(workspace_dev, b->n);
     const bool udp = (flags & RPKT_COALESCE_UDP) != 0u;
     RPKT_TRY(launch_batch(udp ? coalesce_plan_kernel<true> : coalesce_plan_kernel<false>, kSegBlock, 0,
                           stream, *b, recs_dev, order_dev, flags & RPKT_COALESCE_TRUST_SUMS, ws.plan));
-    RPKT_TRY(launch(udp ? coalesce_link_kernel<true> : coalesce_link_kernel<false>, per, blk, 0, st, b->frames_dev, fb, n, ws.plan, ws.aux,
-                    ws.pmax));
-    RPKT_TRY(launch(coalesce_scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
-    RPKT_TRY(launch(coalesce_group_kernel, per, blk, 0, st, n, max_payload, ws.plan, ws.aux, ws.pmax,
-                    ws.obase, ws.part));
-    RPKT_TRY(launch(scan_parts_kernel, dim3(1), blk, 0, st, ws.part, nb, totals_dev,
-                    (uint32_t*)nullptr));
-    RPKT_TRY(launch(coalesce_place_kernel, per, blk, 0, st, n, ws.plan, ws.part, totals_dev, ws.obase,
-                    src_first_dev, out_mss_dev, out_offsets_dev, out_cap, (uint32_t)out_bytes));
-    const uint64_t cper = (uint64_t)kWavesPerBlock * kCoRun;             // positions a block
-    RPKT_TRY(launch(coalesce_copy_kernel, dim3((uint32_t)(((uint64_t)n + cper - 1) / cper)), blk, 0,
-                    st, b->frames_dev, fb, n, ws.plan, ws.obase, totals_dev, out_frames_dev,
-                    (uint32_t)out_bytes, out_cap, ws.aux));
-    const uint64_t hper = (uint64_t)kWavesPerBlock * kCoHdrRun;          // outputs a block
-    const uint32_t outs = n < out_cap ? n : out_cap;                     // n_out <= both, or overflow
-    return launch(udp ? coalesce_header_kernel<true> : coalesce_header_kernel<false>, dim3((uint32_t)(((uint64_t)outs + hper - 1) / hper)), blk,
-                  0, st, b->frames_dev, fb, n, ws.plan, ws.obase, ws.aux, src_first_dev, totals_dev,
-                  out_frames_dev, (uint32_t)out_bytes, out_cap);
+    return (udp ? link_and_write<true, false> : link_and_write<false, false>)(
+        b, ws, max_payload, out_frames_dev, out_bytes, out_offsets_dev, out_cap, src_first_dev,
+        out_mss_dev, totals_dev, (hipStream_t)stream);
+}
+
+size_t rpkt_gpu_coalesce_tunnel_workspace_bytes(uint32_t n) { return co_ws(nullptr, n, true).bytes; }
+
+int rpkt_gpu_coalesce_tunnel_batch(const rpkt_batch_t* b, const rpkt_rec_t* outer_dev,
+                                   const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                   const uint32_t* order_dev, uint32_t max_payload, uint32_t flags,
+                                   uint8_t* out_frames_dev, uint64_t out_bytes,
+                                   uint32_t* out_offsets_dev, uint32_t out_cap,
+                                   uint32_t* src_first_dev, uint16_t* out_mss_dev,
+                                   uint64_t* totals_dev, void* workspace_dev, void* stream) {
+    RPKT_TRY(reframe_args_ok(b, outer_dev, max_payload, flags,
+                             RPKT_COALESCE_TRUST_SUMS | RPKT_COALESCE_UDP, out_frames_dev, out_bytes,
+                             out_offsets_dev, out_cap, src_first_dev, totals_dev, workspace_dev,
+                             tun_dev, inner_dev));
+    if (b->n == 0) return RPKT_OK;
+
+    const CoWs ws = co_ws(workspace_dev, b->n, true);
+    const bool udp = (flags & RPKT_COALESCE_UDP) != 0u;
+    RPKT_TRY(launch_batch(udp ? coalesce_tunnel_plan_kernel<true> : coalesce_tunnel_plan_kernel<false>,
+                          kSegBlock, 0, stream, *b, outer_dev, tun_dev, inner_dev, order_dev,
+                          flags & RPKT_COALESCE_TRUST_SUMS, ws.plan, ws.tplan));
+    return (udp ? link_and_write<true, true> : link_and_write<false, true>)(
+        b, ws, max_payload, out_frames_dev, out_bytes, out_offsets_dev, out_cap, src_first_dev,
+        out_mss_dev, totals_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -80,16 +80,7 @@ constexpr uint32_t kSegOn = 1u, kSegV6 = 2u, kSegUdp = 4u;
 
 // ---- 1. plan ---------------------------------------------------------------------------
 
-// The header bytes of a flat frame at `off` of the frames buffer: dw(x), header bytes
-// x .. x + 3 as a little-endian dword; sum(a, b), the big-endian RFC 1071 sum of [a, b).
-struct FlatHeader {
-    __amdgpu_buffer_rsrc_t rs;
-    uint32_t fb, off;
-    __device__ __forceinline__ uint32_t dw(uint32_t x) const { return gdword(rs, fb, off + x); }
-    __device__ __forceinline__ uint32_t sum(uint32_t a, uint32_t b) const {
-        return range_be_sum(rs, fb, off + a, off + b);
-    }
-};
+// The header bytes of a flat frame: FlatHeader (rpkt_segcopy.h).
 
 // Plan words 2..7 of a segmented frame from its header H: the constants all its segments
 // share.
@@ -320,11 +311,7 @@ void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
 // ---- 3. write --------------------------------------------------------------------------
 
 // Output k of a segmented frame with plan (pa, pb) and output byte base `base`: where it
-// goes and which payload bytes it carries.
-struct SegOut {
-    bool v6, last;
-    uint32_t l3, l4, po, done, pk, d0;
-};
+// goes and which payload bytes it carries (SegOut: rpkt_segcopy.h).
 __device__ __forceinline__ SegOut seg_out(u32x4 pa, u32x4 pb, uint32_t mss, uint32_t k,
                                           uint32_t base) {
     SegOut o;
@@ -614,96 +601,10 @@ void segment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
 // under it and the payload sum the copy returned for the inner checksum: the payload is
 // summed once.  A patch or the payload at an odd distance from the origin enters byte-swapped
 // (it cannot happen in a frame that parsed: every header in between is even).
-constexpr uint32_t kTunOn = 8u, kTunV6 = 16u, kTunUdp = 32u, kTunGtp = 64u, kTunCsum = 128u;
-constexpr int kTunPatches = 9;
-
-// What the outer record (dwords 0, 5, 7, 8, 16) and the tunnel record say about the carrier of
-// an inner frame at `in`: ok, the outer headers are ones the write can fix up and the offsets
-// nest (outer l3 + 20 (IPv6: 40) <= l4; VXLAN / GTP-U: status OK, protocol 17, l4 + 8 <=
-// tun_off; GRE: protocol 47, l4 == tun_off; tun_off + 8 (GRE: 4) <= inner_off <= inner l3).
-struct TunWhere {
-    bool ok, v6, udp, gtp;
-    uint32_t l3, l4, toff, ioff, pdst;
-};
-__device__ __forceinline__ TunWhere tun_where(uint32_t w0, uint32_t w5, uint32_t w7, uint32_t w8,
-                                              uint32_t w16, u32x4 t, const L4Where& in) {
-    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
-    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
-    const bool v6 = det == 0x86ddu;
-    const uint32_t proto = (w8 >> 8) & 0xffu, frag = w7 >> 16, pdst = w8 >> 16;
-    const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16;
-    const uint32_t kind = t.x & 0xffu, toff = t.x >> 16, ioff = t.y & 0xffffu;
-    const bool gre = kind == RPKT_TUN_GRE, gtp = kind == RPKT_TUN_GTPU;
-    const bool carrier = gre ? (proto == 47u && l4 == toff)
-                             : ((kind == RPKT_TUN_VXLAN || gtp) && status == RPKT_S_OK &&
-                                proto == 17u && l4 + 8u <= toff);
-    const bool nest = l4 >= l3 && (v6 ? l4 - l3 >= 40u : (l4 - l3 >= 20u && l4 - l3 <= 60u)) &&
-                      toff + (gre ? 4u : 8u) <= ioff && ioff <= in.l3;
-    const bool ok = carrier && (v6 || det == 0x0800u) && (v6 || (frag & 0x3fffu) == 0u) && nest;
-    return TunWhere{ok, v6, !gre, gtp, l3, l4, toff, ioff, pdst};
-}
-
-// Plan words 8..11 (q[0..3]) and the tunnel bits of word 7 for a frame whose inner frame `s` is
-// cut; false when the GRE header forbids it (the S or R bit, or C without room for its word).
-template <class Header>
-__device__ __forceinline__ bool tunnel_constants(const Header& H, const L4Where& s,
-                                                 const TunWhere& w, uint32_t (&q)[4],
-                                                 uint32_t& bits) {
-    const uint32_t l3 = w.l3, l4 = w.l4, toff = w.toff, po = s.po;
-    bool csum;
-    uint32_t origin, c = 0;
-    if (w.udp) {
-        csum = (H.dw(l4 + 4u) >> 16) != 0u;                      // a zero checksum stays zero
-        origin = l4;
-        if (csum) {
-            if (!w.v6) {
-                c = 17u + H.sum(l3 + 12u, l3 + 20u);
-            } else {
-                const uint32_t pd = ip6_pseudo_dst(w.pdst, l3, l4);
-                c = 17u + H.sum(l3 + 8u, l3 + 24u) + H.sum(pd, pd + 16u);
-            }
-        }
-    } else {
-        const uint32_t g0 = H.dw(toff) & 0xffu;                  // C 0x80, R 0x40, K 0x20, S 0x10
-        csum = (g0 & 0x80u) != 0u;
-        if ((g0 & 0x50u) || (csum && toff + 8u > w.ioff)) return false;
-        origin = toff;
-    }
-    if (csum) {
-        // [origin, po) without the bytes the write patches: each leaves by its complement
-        c += H.sum(origin, po);
-        auto drop = [&](uint32_t off, uint32_t n) {
-            const uint32_t v = H.sum(off, off + n);
-            c += 0xffffu ^ (((off - origin) & 1u) ? bswap16(v) : v);
-        };
-        if (w.udp) drop(l4 + 4u, 4u); else drop(toff + 4u, 2u);
-        if (w.gtp) drop(toff + 2u, 2u);
-        if (s.v6) {
-            drop(s.l3 + 4u, 2u);
-        } else {
-            drop(s.l3 + 2u, 4u);
-            drop(s.l3 + 10u, 2u);
-        }
-        drop(s.l4 + 4u, 4u);
-        if (!s.udp) {
-            drop(s.l4 + 13u, 1u);
-            drop(s.l4 + 16u, 2u);
-        }
-    }
-    uint32_t opc = 0, oident = 0;
-    if (!w.v6) {
-        const uint32_t ip0 = H.dw(l3), ip1 = H.dw(l3 + 4u), ip2 = H.dw(l3 + 8u);
-        oident = be16_lo(ip1);
-        opc = H.sum(l3, l4) + (0xffffu ^ be16_hi(ip0)) + (0xffffu ^ oident) + (0xffffu ^ be16_hi(ip2));
-    }
-    q[0] = l3 | (l4 << 16);
-    q[1] = toff;
-    q[2] = fold16(opc) | (oident << 16);
-    q[3] = fold16(c);
-    bits = kTunOn | (w.v6 ? kTunV6 : 0u) | (w.udp ? kTunUdp : 0u) | (w.gtp ? kTunGtp : 0u) |
-           (csum ? kTunCsum : 0u);
-    return true;
-}
+// The kTun* bits, the carrier rule (TunWhere, tun_where), the constants (tunnel_constants) and
+// the outer patches (tunnel_patches) are in rpkt_segcopy.h: rpkt_gpu_coalesce_tunnel_batch
+// (rpkt_coalesce.hip) judges a carrier by the same rule and writes a merged frame's outer
+// headers as segment 0 of a cut.
 
 template <bool kUdp>
 __global__ __launch_bounds__(kSegBlock)
@@ -765,47 +666,6 @@ void segment_tunnel_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         plan[4 * (size_t)i + 3] = u32x4{0u, 0u, 0u, 0u};
     }
     plan_store<4>(valid, i, p, cnt, bytes, plan, seg_first, obase, part, red);
-}
-
-// The outer headers' patches of output k, P[5..8], after the inner ones P[0..4]; pc: plan
-// words 8..11, `pay` the payload's big-endian sum.
-__device__ __forceinline__ void tunnel_patches(const SegOut& o, u32x4 pb, u32x4 pc, uint32_t k,
-                                               uint32_t pay, SegPatch (&P)[kTunPatches]) {
-    P[5] = P[6] = P[7] = P[8] = SegPatch{0u, 0u, 0u};
-    if (!(pb.w & kTunOn)) return;                                 // wave-uniform
-    const uint32_t l3 = pc.x & 0xffffu, l4 = pc.x >> 16, toff = pc.y & 0xffffu;
-    const uint32_t tot = o.po + o.pk;
-    if (!(pb.w & kTunV6)) {
-        const uint32_t tlen = (tot - l3) & 0xffffu, ident = ((pc.z >> 16) + k) & 0xffffu;
-        const uint32_t ck = ~fold16((pc.z & 0xffffu) + tlen + ident) & 0xffffu;
-        P[5] = SegPatch{l3 + 2u, 4u, bswap16(tlen) | (bswap16(ident) << 16)};
-        P[6] = SegPatch{l3 + 10u, 2u, bswap16(ck)};
-    } else {
-        P[5] = SegPatch{l3 + 4u, 2u, bswap16((tot - l3 - 40u) & 0xffffu)};
-    }
-    if (pb.w & kTunGtp) P[7] = SegPatch{toff + 2u, 2u, bswap16((tot - toff - 8u) & 0xffffu)};
-    const bool udp = (pb.w & kTunUdp) != 0u, csum = (pb.w & kTunCsum) != 0u;
-    const uint32_t origin = udp ? l4 : toff;
-    uint32_t sum = 0;
-    if (csum) {
-        sum = pc.w + (((o.po - origin) & 1u) ? bswap16(pay) : pay);
-        // the inner patches and the GTP-U length lie under the outer checksum
-        const int under[6] = {0, 1, 2, 3, 4, 7};
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const SegPatch& x = P[under[u]];
-            const uint32_t v = x.n >= 4u ? x.val : x.val & ((1u << (8u * x.n)) - 1u);
-            sum += be_sum((v & 0xffffu) + (v >> 16), x.off - origin);
-        }
-    }
-    if (udp) {
-        // the length is in the pseudo header and in the header
-        const uint32_t ulen = (tot - l4) & 0xffffu;
-        const uint32_t uck = csum ? udp_csum_field(sum + 2u * ulen) : 0u;
-        P[8] = SegPatch{l4 + 4u, 4u, bswap16(ulen) | (bswap16(uck) << 16)};
-    } else if (csum) {
-        P[8] = SegPatch{toff + 4u, 2u, bswap16(~fold16(sum) & 0xffffu)};   // RFC 2784: 0 stays 0
-    }
 }
 
 // write_output for the 64-B plan (pa, pb, pc)

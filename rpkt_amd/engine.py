@@ -92,6 +92,9 @@ ABI = {
     "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p, _p]),
+    "rpkt_gpu_coalesce_tunnel_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_coalesce_tunnel_batch": (_i, [_B, _p, _p, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p,
+                                            _u32, _p, _p, _p, _p, _p]),
     "rpkt_gpu_options_batch":(_i, [_B, _p, _p, _p]),
     "rpkt_gpu_options_batch_compact": (_i, [_B, _p, _p, _p]),
     "rpkt_gpu_parse_options_batch": (_i, [_B, _u32, _p, _p, _p, _u32, _p]),
@@ -758,6 +761,44 @@ def coalesce_batch(batch, recs, order=None, max_payload=65535, trust_sums=False,
         raise RpktError("coalesce_batch: out_mss takes %d 16-bit entries" % n)
     _call("rpkt_gpu_coalesce_batch", ctypes.byref(batch.desc()), recs.data_ptr(), _ptr(order),
           max_payload, (COALESCE_TRUST_SUMS if trust_sums else 0) | (COALESCE_UDP if udp else 0),
+          out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, src_first.data_ptr(),
+          _ptr(out_mss), totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), src_first, totals
+
+
+def coalesce_tunnel_workspace(n, device="cuda"):
+    """The workspace tensor of coalesce_tunnel_batch for n positions
+    (rpkt_gpu_coalesce_tunnel_workspace_bytes)."""
+    return _workspace("coalesce_tunnel", n, device)
+
+
+def coalesce_tunnel_batch(batch, outer, tun, inner, order=None, max_payload=65535, trust_sums=False,
+                          out_frames=None, out_offsets=None, out_cap=None, out_bytes=None,
+                          src_first=None, out_mss=None, totals=None, workspace=None, stream=None,
+                          udp=False):
+    """rpkt_gpu_coalesce_tunnel_batch: receive coalescing (GRO) of the inner TCP (with udp=True,
+    RPKT_COALESCE_UDP, also the inner UDP) of the VXLAN / GTP-U / GRE frames of `batch`, with the
+    outer lengths and checksums repaired: the inverse of segment_tunnel_batch.  `outer`, `tun`,
+    `inner` are parse_tunnel_batch's three tensors for this batch (both sums unless trust_sums).
+    A frame without a tunnel is merged as coalesce_batch merges it with its outer record.
+    `order`, `max_payload`, `out_mss`, the default sizes and the return value (out, src_first,
+    totals) are coalesce_batch's.  The flow events of parse_tunnel_batch(..., RPKT_F_FLOW_EV)
+    are keyed by the inner flow where the tunnel decoded, so flow_order on them already
+    brings each inner flow's segments together."""
+    n = batch.n
+    out_frames, out_bytes, out_offsets, out_cap, src_first, totals, workspace = _reframe_outputs(
+        "coalesce_tunnel_batch", batch, outer, lambda: max(n, 1), lambda cap: batch.frames.numel(),
+        out_frames, out_offsets, out_cap, out_bytes, src_first, "src_first", totals, workspace,
+        "coalesce_tunnel")
+    if tun.numel() != n * 16 or inner.numel() != n * REC_BYTES:
+        raise RpktError("coalesce_tunnel_batch: tunnel or inner records do not fit %d frames" % n)
+    if order is not None and (order.numel() < n or order.element_size() != 4):
+        raise RpktError("coalesce_tunnel_batch: order takes %d 32-bit entries" % n)
+    if out_mss is not None and (out_mss.numel() < n or out_mss.element_size() != 2):
+        raise RpktError("coalesce_tunnel_batch: out_mss takes %d 16-bit entries" % n)
+    _call("rpkt_gpu_coalesce_tunnel_batch", ctypes.byref(batch.desc()), outer.data_ptr(),
+          tun.data_ptr(), inner.data_ptr(), _ptr(order), max_payload,
+          (COALESCE_TRUST_SUMS if trust_sums else 0) | (COALESCE_UDP if udp else 0),
           out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, src_first.data_ptr(),
           _ptr(out_mss), totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
     return DeviceBatch(out_frames, out_cap, out_offsets), src_first, totals

@@ -28,7 +28,19 @@ adds the same workload as UDP datagrams (tools/segment_time.py --udp's: a 42-byt
 32,768 B of payload, cut at 1448 with RPKT_SEGMENT_UDP) coalesced with RPKT_COALESCE_UDP, in
 the same interleaved rounds as the TCP leg (flags 0) and the device copy:
 `udp_over_tcp_per_byte` and `udp_over_copy_per_byte` are same-run ratios.  Every output must
-be the source datagram byte for byte but its checksum field, which the source leaves 0."""
+be the source datagram byte for byte but its checksum field, which the source leaves 0.
+
+    python tools/coalesce_time.py --tunnel [--out profiles/coalesce/tunnel/times.json]
+
+adds rpkt_gpu_coalesce_tunnel_batch: tools/segment_time.py --tunnel's workload (the same inner
+super-frames behind 50 bytes of outer Ether / IPv4 / UDP / VXLAN, cut at 1448 by
+rpkt_gpu_segment_tunnel_batch), located by a tunnel parse with both sums and coalesced back,
+in the same interleaved rounds as the flat leg and the device copy:
+`tunnel_over_tcp_per_output_byte` (the times over the output frame bytes),
+`tunnel_over_tcp_per_byte` and `tunnel_over_copy_per_byte` (over the bytes moved) are same-run
+ratios.  Every output must be the source frame byte for byte but the two checksum fields the
+source leaves unfilled (the inner TCP's and the outer UDP's).  With --trace-launches the traced
+calls are the tunnel entry's."""
 import argparse
 import json
 import os
@@ -40,8 +52,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from segment_time import (HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, UDP_HDR, super_frames, time_legs,  # noqa: E402
-                          udp_super_frames)
+from segment_time import (HBM_BYTES_PER_S, HDR, MSS, PAYLOAD, TUN_HDR, UDP_HDR, super_frames,  # noqa: E402
+                          time_legs, udp_super_frames, vxlan_prefix)
 
 
 def main():
@@ -49,13 +61,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--udp", action="store_true",
                     help="also time RPKT_COALESCE_UDP on the same workload as UDP datagrams")
+    ap.add_argument("--tunnel", action="store_true",
+                    help="also time rpkt_gpu_coalesce_tunnel_batch on the same frames behind VXLAN")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace or counter pass")
     a = ap.parse_args()
-    a.out = a.out or ("profiles/udp_reframe/coalesce_times.json" if a.udp else "profiles/coalesce/times.json")
+    a.out = a.out or ("profiles/udp_reframe/coalesce_times.json" if a.udp else
+                      "profiles/coalesce/tunnel/times.json" if a.tunnel else "profiles/coalesce/times.json")
     import torch
     from rpkt_amd import engine
     from rpkt_amd.records import as_records
@@ -96,12 +111,37 @@ def main():
                              out_offsets=out_offsets, out_cap=n_seg, out_bytes=seg_bytes,
                              seg_first=first, totals=totals, workspace=sws, stream=stream)
 
+    legs = {"coalesce_batch": coalesce, "device_copy": copy, "segment_batch": segment}
+    if a.tunnel:
+        tlen, tseg_bytes = TUN_HDR + flen, n * (per * (TUN_HDR + HDR) + PAYLOAD)
+        prefix = torch.from_numpy(vxlan_prefix()).to("cuda")
+        tsrcs, tsegs, trecs = [], [], []
+        for db in srcs:
+            tdb = engine.DeviceBatch(torch.cat([prefix.expand(n, TUN_HDR), db.frames.view(n, flen)],
+                                               dim=1).reshape(-1).contiguous(), n, stride=tlen)
+            tsrcs.append(tdb)
+            sdb, _, tot = engine.segment_tunnel_batch(tdb, *engine.parse_tunnel_batch(tdb, 0), MSS,
+                                                      out_cap=n_seg, out_bytes=tseg_bytes)
+            assert tot.cpu().tolist() == [n_seg, tseg_bytes]
+            tsegs.append(sdb)
+            trecs.append(engine.parse_tunnel_batch(sdb, 3))
+        tun_out = torch.empty(n * tlen, dtype=torch.uint8, device="cuda")
+        tun_offsets, tun_first = torch.empty_like(out_offsets), torch.empty_like(first)
+        tun_mss, tun_totals = torch.empty_like(out_mss), torch.zeros_like(totals)
+        tws = engine.coalesce_tunnel_workspace(n_seg)
+
+        def coalesce_tunnel(k):
+            engine.coalesce_tunnel_batch(tsegs[k % R], *trecs[k % R], out_frames=tun_out,
+                                         out_offsets=tun_offsets, out_cap=n, out_bytes=n * tlen,
+                                         src_first=tun_first, out_mss=tun_mss, totals=tun_totals,
+                                         workspace=tws, stream=stream)
+
+        legs = {"coalesce_tunnel": coalesce_tunnel, **legs}
     if a.trace_launches:
         for k in range(a.trace_launches):
-            coalesce(k)
+            (coalesce_tunnel if a.tunnel else coalesce)(k)
         torch.cuda.synchronize()
         return
-    legs = {"coalesce_batch": coalesce, "device_copy": copy, "segment_batch": segment}
     if a.udp:
         ulen, useg_bytes = UDP_HDR + PAYLOAD, n * (per * UDP_HDR + PAYLOAD)
         usrcs, usegs, urecs = [], [], []
@@ -156,6 +196,24 @@ def main():
         assert (urec["ip_sum"] == 0xffff).all() and (urec["l4_sum"] == 0xffff).all()
         assert (urec["payload_len"] == PAYLOAD).all()
 
+    for k in range(R if a.tunnel else 0):                         # the tunnel output is its source too
+        from rpkt_amd.records import as_tunnels
+        tun_out.fill_(0xa5)
+        coalesce_tunnel(k)
+        torch.cuda.synchronize()
+        assert tun_totals.cpu().tolist() == [n, n * tlen], tun_totals.cpu().tolist()
+        assert torch.equal(tun_first[:n + 1], first[:n + 1]) and (tun_mss[:n] == MSS).all().item()
+        got, src = tun_out.view(n, tlen), tsrcs[k].frames.view(n, tlen)
+        uc, tc = 14 + 20 + 6, TUN_HDR + 50                        # the outer UDP and inner TCP checksums
+        for lo, hi in ((0, uc), (uc + 2, tc), (tc + 2, tlen)):
+            assert torch.equal(got[:, lo:hi], src[:, lo:hi]), (lo, hi)
+        to, tt, ti = engine.parse_tunnel_batch(engine.DeviceBatch(tun_out, n, tun_offsets), 3)
+        to, tt, ti = as_records(to.cpu().numpy()), as_tunnels(tt.cpu().numpy()), as_records(ti.cpu().numpy())
+        assert (to["status"] == 0).all() and (tt["status"] == 0).all() and (ti["status"] == 0).all()
+        assert (to["ip_sum"] == 0xffff).all() and (to["l4_sum"] == 0xffff).all()
+        assert (ti["ip_sum"] == 0xffff).all() and (ti["l4_sum"] == 0xffff).all()
+        assert (ti["payload_len"] == PAYLOAD).all()
+
     moved = {"frames_in": seg_bytes, "records_in": n_seg * 80, "offsets_in": (n_seg + 1) * 4,
              "frames_out": n * flen, "offsets_out": (n + 1) * 4, "src_first_out": (n_seg + 1) * 4,
              "out_mss_out": n_seg * 2}
@@ -175,6 +233,19 @@ def main():
         res["ms"]["coalesce_udp"]["bytes"] = ualg
         res["ms"]["coalesce_udp"]["fraction_of_8TBs"] = round(
             ualg / (med["coalesce_udp"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    if a.tunnel:
+        # two more 80-B records and a 16-B tunnel record a position
+        talg = alg - seg_bytes - n * flen + tseg_bytes + n * tlen + n_seg * (80 + 16)
+        res["tunnel"] = {"frame_len": tlen, "bytes": talg, "frames_out": n * tlen}
+        res["ms"]["coalesce_tunnel"]["bytes"] = talg
+        res["ms"]["coalesce_tunnel"]["fraction_of_8TBs"] = round(
+            talg / (med["coalesce_tunnel"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        res["tunnel_over_tcp_per_output_byte"] = round(
+            (med["coalesce_tunnel"] / (n * tlen)) / (med["coalesce_batch"] / (n * flen)), 4)
+        res["tunnel_over_tcp_per_byte"] = round(
+            (med["coalesce_tunnel"] / talg) / (med["coalesce_batch"] / alg), 4)
+        res["tunnel_over_copy_per_byte"] = round(
+            (med["coalesce_tunnel"] / talg) / (med["device_copy"] / (2 * seg_bytes)), 4)
     per_byte = {name: med[name] / res["ms"][name]["bytes"] for name in legs}
     if a.udp:
         res["udp_over_tcp_per_byte"] = round(per_byte["coalesce_udp"] / per_byte["coalesce_batch"], 4)

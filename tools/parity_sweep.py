@@ -21,7 +21,8 @@ parse's records, or the flat oracle's of the flattened bytes, which gather heade
 cuts), a generator batch through rpkt_gpu_segment_batch and its output through
 rpkt_gpu_coalesce_batch with random flags (RPKT_SEGMENT_UDP, RPKT_COALESCE_UDP, TRUST_SUMS)
 against the same model, a tunnel batch (config 13 / 14) through rpkt_gpu_segment_tunnel_batch at a
-random mss and flag against tests/segment_tunnel_model.py, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
+random mss and flag against tests/segment_tunnel_model.py, its output through
+rpkt_gpu_coalesce_tunnel_batch with random flags against tests/coalesce_tunnel_model.py, and a fuzzed tunnel chain batch (config 14, or tests/tunnel_frames.py frames with
 random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py; (d)
 a nested tunnel batch (tests/nested_tunnel_ref.py's recipe: config 13 / 14 frames, frame k
 wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level passes
@@ -44,6 +45,7 @@ from rpkt_amd import engine, gen  # noqa: E402
 from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_records,  # noqa: E402
                               as_records16, as_tunnels, project16)
 
+import coalesce_tunnel_model  # noqa: E402
 import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
 import segment_chains_model  # noqa: E402
@@ -293,6 +295,36 @@ def check_segment_tunnel(rng, seed):
             "cut": [kinds[k] for k in (0, 1, 2, 3)]}
 
 
+def check_coalesce_tunnel(rng, seed):
+    """A config 13 / 14 batch cut in the tunnel (the model's segments at a random mss), then
+    rpkt_gpu_coalesce_tunnel_batch of the segments with random flags and max_payload against
+    tests/coalesce_tunnel_model.py."""
+    import torch
+    cfg = int(rng.choice([13, 14]))
+    hb = gen.make_batch(cfg, n=int(rng.integers(1, 1500)), seed=seed)
+    mss = int(rng.choice([16, 17, 100, 300, 536, 1448]))
+    udp = bool(rng.random() < 0.5)
+    segs = segment_tunnel_model.segment(hb, *segment_tunnel_model.tunnel_records(hb), mss, udp)[0]
+    shb = segment_model.pack(segs)
+    cudp, trust = bool(rng.random() < 0.5), bool(rng.random() < 0.3)
+    max_payload = int(rng.choice([1, 1000, 9000, 65535]))
+    srecs = segment_tunnel_model.tunnel_records(shb)
+    out, first, totals, mss_out = coalesce_tunnel_model.coalesce(shb, *srecs, None, max_payload, trust, cudp)
+    cap = int(totals[0]) + int(rng.integers(0, 9))
+    sdb = engine.DeviceBatch.from_host(shb)
+    gm = torch.zeros(shb.n, dtype=torch.int16, device="cuda")
+    cdb, gf, gt = engine.coalesce_tunnel_batch(sdb, *engine.parse_tunnel_batch(sdb, segment_model.F6), None,
+                                               max_payload, trust, out_cap=cap,
+                                               out_bytes=int(totals[1]) + int(rng.integers(0, 40)),
+                                               out_mss=gm, udp=cudp)
+    same_reframed("coalesce_tunnel_batch", cdb, gf, gt, out, first, totals, cap)
+    assert np.array_equal(gm.cpu().numpy().view(np.uint16), mss_out), "coalesce_tunnel_batch out_mss"
+    kinds = coalesce_tunnel_model.merged_kinds(first, totals[0], srecs[1])
+    return {"cfg": cfg, "n": int(hb.n), "mss": mss, "udp": udp, "coalesce_udp": cudp, "trust": trust,
+            "max_payload": max_payload, "n_seg": int(shb.n), "n_out": int(totals[0]),
+            "merged": [kinds[k] for k in (0, 1, 2, 3)]}
+
+
 def check_tunnel_chains(rng, seed):
     """rpkt_gpu_parse_tunnel_chains (records and flow events) against the model."""
     if rng.random() < 0.7:
@@ -368,6 +400,8 @@ def main():
                 rec["segment_coalesce"] = check_segment_coalesce(rng, seed)
                 step = "segment_tunnel"
                 rec["segment_tunnel"] = check_segment_tunnel(rng, seed)
+                step = "coalesce_tunnel"
+                rec["coalesce_tunnel"] = check_coalesce_tunnel(rng, seed)
                 step = "tunnel_chains"
                 rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
                 step = "tunnel_next"
