@@ -415,6 +415,18 @@ extern "C" {
                                          out_bytes: u64, out_offsets_dev: *mut u32, out_cap: u32,
                                          seg_first_dev: *mut u32, totals_dev: *mut u64,
                                          workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_segment_tunnel_chains for n_chains chains.
+    pub fn rpkt_gpu_segment_tunnel_chains_workspace_bytes(n_chains: u32) -> usize;
+    /// rpkt_gpu_segment_tunnel_batch over mbuf chains, read in place, located by
+    /// rpkt_gpu_parse_tunnel_chains' three record arrays: every output is what the flat entry
+    /// writes for the chains' bytes in order; the output is a packed, flat batch.
+    pub fn rpkt_gpu_segment_tunnel_chains(chains: *const rpkt_chains_t,
+                                          outer_dev: *const rpkt_rec_t,
+                                          tun_dev: *const rpkt_tun_t, inner_dev: *const rpkt_rec_t,
+                                          mss: u32, flags: u32, out_frames_dev: *mut u8,
+                                          out_bytes: u64, out_offsets_dev: *mut u32, out_cap: u32,
+                                          seg_first_dev: *mut u32, totals_dev: *mut u64,
+                                          workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
     /// Workspace of rpkt_gpu_coalesce_batch for n positions.
     pub fn rpkt_gpu_coalesce_workspace_bytes(n: u32) -> usize;
     /// TCP receive coalescing (GRO / LRO) on the device: consecutive in-order TCP segments of

@@ -520,6 +520,33 @@ pub unsafe fn segment_tunnel_batch(batch: &ffi::rpkt_batch_t, outer_dev: *const 
                                              workspace_dev, stream))
 }
 
+/// rpkt_gpu_segment_tunnel_chains_workspace_bytes: the workspace of segment_tunnel_chains for
+/// `n_chains`.
+pub fn segment_tunnel_chains_workspace_bytes(n_chains: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_segment_tunnel_chains_workspace_bytes(n_chains) }
+}
+
+/// rpkt_gpu_segment_tunnel_chains: segment_tunnel_batch over mbuf chains, read in place (no
+/// gather into a flat batch first); `mss` and `flags` as there.  `out` is laid out as
+/// segment_batch's: the output is a packed, flat batch of wire frames.
+///
+/// # Safety
+/// `chains` must describe device memory valid for the call; `outer_dev`, `tun_dev` and
+/// `inner_dev` must be what parse_tunnel_chains wrote for these same chains (16-byte aligned);
+/// every pointer of `out` must be device memory of the size its field documents, and
+/// `workspace_dev` must hold `segment_tunnel_chains_workspace_bytes(chains.n_chains)` bytes
+/// (16-byte aligned), all on the same device.
+pub unsafe fn segment_tunnel_chains(chains: &ffi::rpkt_chains_t, outer_dev: *const Rec,
+                                    tun_dev: *const ffi::rpkt_tun_t, inner_dev: *const Rec,
+                                    mss: u32, flags: u32, out: &SegmentOut,
+                                    workspace_dev: *mut core::ffi::c_void,
+                                    stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_segment_tunnel_chains(chains, outer_dev, tun_dev, inner_dev, mss, flags,
+                                              out.frames_dev, out.out_bytes, out.offsets_dev,
+                                              out.out_cap, out.seg_first_dev, out.totals_dev,
+                                              workspace_dev, stream))
+}
+
 /// The outputs of rpkt_gpu_coalesce_batch: a packed batch of `out_cap` slots (`frames_dev`,
 /// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first
 /// position of every output (`src_first_dev`, `n + 1` entries), each merged output's segment

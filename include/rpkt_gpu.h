@@ -114,6 +114,8 @@ enum rpkt_status {
  *     (E_ALIGN): segs_dev and totals_dev 8 B, recs_dev, out_frames_dev, workspace_dev 16 B;
  *   rpkt_gpu_segment_tunnel_batch: rpkt_gpu_segment_batch's order with outer_dev, tun_dev and
  *     inner_dev in recs_dev's places: each required (E_INVAL) and 16-byte aligned (E_ALIGN);
+ *   rpkt_gpu_segment_tunnel_chains: rpkt_gpu_segment_chains' order with the same three in
+ *     recs_dev's places;
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
@@ -830,8 +832,9 @@ int rpkt_gpu_segment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev
  * rpkt_gpu_parse_batch over out_cap slots captures as one graph.
  * Bounds for sizing: rpkt_gpu_segment_batch's with the sum of the chains' pkt_len in
  * frames_bytes' place; that sum is at most buf_bytes when segments do not overlap.
- * Not covered: coalescing over chains; the inner TCP or UDP of tunnelled frames over chains
- * (rpkt_gpu_segment_tunnel_batch, below, takes flat batches only). */
+ * A tunnelled chain is to this entry what its outer record says, as a tunnelled frame is to
+ * rpkt_gpu_segment_batch; rpkt_gpu_segment_tunnel_chains (below) cuts the inner TCP or UDP.
+ * Not covered: coalescing over chains. */
 size_t rpkt_gpu_segment_chains_workspace_bytes(uint32_t n_chains);
 int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_dev, uint32_t mss,
                             uint32_t flags, uint8_t* out_frames_dev, uint64_t out_bytes,
@@ -901,7 +904,8 @@ int rpkt_gpu_segment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_
  * the output's, and offsets that do not nest as above make the frame pass through: wrong
  * frames, never a fault.
  * The inverse is rpkt_gpu_coalesce_tunnel_batch (below).
- * Not covered: tunnel segmentation over mbuf chains, nested
+ * Over mbuf chains: rpkt_gpu_segment_tunnel_chains (below).
+ * Not covered: nested
  * tunnels (only the level-1 records are accepted: the inner frame of a second tunnel level is
  * payload here), a segment size per flow, GRE sequence numbers, turning a zero outer UDP
  * checksum into a filled one. */
@@ -912,6 +916,39 @@ int rpkt_gpu_segment_tunnel_batch(const rpkt_batch_t* batch, const rpkt_rec_t* o
                                   uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
                                   uint32_t* seg_first_dev, uint64_t* totals_dev, void* workspace_dev,
                                   void* stream);
+
+/* The same over mbuf chains: the case a tunnel endpoint meets, since a super-frame is larger
+ * than one data room and so a chain.  The chains are read in place, the output is linear.
+ *
+ * Let F_p be chain p's bytes in order under rpkt_chains_t's clamps, as rpkt_gpu_segment_chains
+ * defines them.  Every output -- out_frames_dev, out_offsets_dev, seg_first_dev, totals_dev --
+ * is byte for byte what rpkt_gpu_segment_tunnel_batch writes for the packed batch
+ * F_0 .. F_{n_chains-1} with the same outer_dev, tun_dev, inner_dev, mss, flags, out_cap and
+ * out_bytes: its three rules (no tunnel, undecoded, decoded), every header fix-up, the overflow
+ * contract, the spare offset slots, and nothing written outside the buffers.
+ *   Records   normally the three outputs of rpkt_gpu_parse_tunnel_chains on these chains: their
+ *             offsets are logical positions in F_p already.  An outer, tunnel or inner header
+ *             that straddles a segment end is a parse error or RPKT_T_BAD there, so such a chain
+ *             passes through.  The entry itself puts no condition on where segments are cut:
+ *             with records that say "cut" (a tunnel parse of the flattened bytes), the header
+ *             [0, I.payload_off) and the payload are gathered across any cuts.
+ *   Nesting   pkt_len takes frame_len's place in the nesting tests and in the payload_len clamp.
+ * Overlap, Huge, Faults and Limits are rpkt_gpu_segment_chains' word for word.  flags: 0 or
+ * RPKT_SEGMENT_UDP.  workspace_dev: rpkt_gpu_segment_tunnel_chains_workspace_bytes(n_chains)
+ * bytes, 16-byte aligned; calls that share one must be ordered.  No host step:
+ * rpkt_gpu_parse_tunnel_chains -> rpkt_gpu_segment_tunnel_chains -> rpkt_gpu_parse_tunnel_batch
+ * over out_cap slots captures as one graph.
+ * Bounds for sizing: rpkt_gpu_segment_tunnel_batch's with the sum of the chains' pkt_len in
+ * frames_bytes' place.  Argument checks: rpkt_gpu_segment_chains' in its order, with tun_dev and
+ * inner_dev required and 16-byte aligned along with outer_dev.
+ * Not covered: what rpkt_gpu_segment_tunnel_batch does not cover; coalescing over chains. */
+size_t rpkt_gpu_segment_tunnel_chains_workspace_bytes(uint32_t n_chains);
+int rpkt_gpu_segment_tunnel_chains(const rpkt_chains_t* chains, const rpkt_rec_t* outer_dev,
+                                   const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                   uint32_t mss, uint32_t flags, uint8_t* out_frames_dev,
+                                   uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
+                                   uint32_t* seg_first_dev, uint64_t* totals_dev,
+                                   void* workspace_dev, void* stream);
 
 /* ---- TCP and UDP receive coalescing (GRO / LRO, UDP GRO) --------------------------- */
 

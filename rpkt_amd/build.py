@@ -134,7 +134,7 @@ def build_gen(force=False):
 
 
 EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "tso_tx_chains", "lro_rx",
-            "vtep_tx", "vtep_gro_rx")
+            "vtep_tx", "vtep_gro_rx", "vtep_tx_chains")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "parse_batch")
 FLOW_REDUCE_BIN = os.path.join(ROOT, "examples", "flow_reduce")
 VTEP_RX_BIN = os.path.join(ROOT, "examples", "vtep_rx")
@@ -143,6 +143,7 @@ TSO_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "tso_tx_chains")
 LRO_RX_BIN = os.path.join(ROOT, "examples", "lro_rx")
 VTEP_TX_BIN = os.path.join(ROOT, "examples", "vtep_tx")
 VTEP_GRO_RX_BIN = os.path.join(ROOT, "examples", "vtep_gro_rx")
+VTEP_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "vtep_tx_chains")
 
 
 def build_example(force=False):

@@ -49,7 +49,8 @@
 // rpkt_gpu_segment_tunnel_batch (the inner TCP / UDP of VXLAN, GTP-U and GRE frames, flat
 // batches) is the flat cut with the inner record plus the outer headers' fix-ups: a plan and a
 // write kernel of its own with a 64-B plan and nine patches, everything else shared; see
-// "tunnels" below.
+// "tunnels" below.  rpkt_gpu_segment_tunnel_chains is that cut over mbuf chains: the chain
+// kernels' walk, cursor and gathered header with the tunnel kernels' plan and patches.
 #include "rpkt_segcopy.h"
 
 namespace {
@@ -727,6 +728,189 @@ void segment_tunnel_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb
     }
 }
 
+// ---- tunnels over mbuf chains ----------------------------------------------------------
+//
+// rpkt_gpu_segment_tunnel_chains is the two above put together: the chain plan's walk for
+// pkt_len and the first non-empty segment with the tunnel plan's three records and 64-B plan,
+// the chain write's cursor and flat-or-gathered header with the tunnel write's nine patches.
+// The header here is [0, inner payload_off): the outer, tunnel and inner headers together.
+
+template <bool kUdp>
+__global__ __launch_bounds__(kSegBlock)
+void segment_tunnel_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
+                                       const uint32_t* __restrict__ segs, uint32_t n_segs,
+                                       const uint32_t* __restrict__ chain_first, uint32_t n,
+                                       const rpkt_rec_t* __restrict__ outer,
+                                       const rpkt_tun_t* __restrict__ tun,
+                                       const rpkt_rec_t* __restrict__ inner, uint32_t mss,
+                                       u32x4* __restrict__ plan, uint32_t* __restrict__ seg_first,
+                                       uint64_t* __restrict__ obase, uint64_t* __restrict__ part) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    uint64_t cnt = 0, bytes = 0;
+    uint32_t p[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, q[4] = {0u, 0u, 0u, 0u};
+
+    if (p0 < n) {                                                 // wave-uniform
+        // the tile's outer records through the stage, then its inner records through the same
+        uint32_t* st = stage[wave];
+        const uint32_t* w = st + lane * 21;
+        stage_records_tile(st, outer, p0, n, lane);
+        const uint32_t o0 = w[0], o5 = w[5], o7 = w[7], o8 = w[8], o16 = w[16], o17 = w[17];
+        wave_sync();
+        stage_records_tile(st, inner, p0, n, lane);
+        const u32x4 t = valid ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tun) + i)
+                              : u32x4{0u, 0u, 0u, 0u};
+        // pkt_len in 64 bits and the first non-empty segment, as segment_chains_plan_kernel
+        const SegTable S{segs, fb};
+        uint32_t a = 0, b = 0;
+        if (valid) chain_range(chain_first, n_segs, i, a, b);
+        uint64_t pkt = 0;
+        Frame s0{fb, 0u};
+        for (uint32_t k = a; k < b; ++k) {
+            const Frame sg = S.seg(k);
+            if (pkt == 0) s0 = sg;
+            pkt += sg.len;
+        }
+        const uint32_t len = pkt < 0xffffffffull ? (uint32_t)pkt : 0xffffffffu;
+        // no tunnel: the chain itself under its outer record; a decoded one: its inner frame
+        const bool tunnel = (t.x & 0xffu) != RPKT_TUN_NONE;
+        L4Where s = l4_where(o0, o5, o7, o8, o16, o17, len, kUdp);
+        TunWhere tw{};
+        if (tunnel) {
+            s = l4_where(w, len, kUdp);
+            tw = tun_where(o0, o5, o7, o8, o16, t, s);
+            s.on = s.on && ((t.x >> 8) & 0xffu) == RPKT_T_OK && tw.ok;
+        }
+        p[0] = a;
+        p[1] = len;
+        if (valid) {
+            cnt = 1;
+            bytes = pkt;
+        }
+        if (valid && s.on && s.pl > mss) {
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
+            uint32_t bits = 0;
+            bool cut;
+            if (__builtin_expect(s.po <= s0.len, 1)) {
+                const FlatHeader H{rs, fb, s0.off};
+                cut = !tunnel || tunnel_constants(H, s, tw, q, bits);
+                if (cut) seg_constants(H, s, p);
+            } else {
+                const GatheredHeader H{S, rs, a, n_segs, s.po};
+                cut = !tunnel || tunnel_constants(H, s, tw, q, bits);
+                if (cut) seg_constants(H, s, p);
+            }
+            if (cut) {                                            // segmented
+                cnt = (s.pl + mss - 1u) / mss;
+                bytes = cnt * s.po + s.pl;
+                p[7] |= bits;
+            }
+        }
+    }
+    if (valid) {
+        plan[4 * (size_t)i + 2] = u32x4{q[0], q[1], q[2], q[3]};
+        plan[4 * (size_t)i + 3] = u32x4{0u, 0u, 0u, 0u};
+    }
+    plan_store<4>(valid, i, p, cnt, bytes, plan, seg_first, obase, part, red);
+}
+
+// chain_state for the 64-B plan: ChainState and plan words 8..11
+struct TunnelChainState {
+    ChainState s;
+    u32x4 pc;
+};
+__device__ __forceinline__ TunnelChainState tunnel_chain_state(const u32x4* __restrict__ plan,
+                                                               const uint64_t* __restrict__ obase,
+                                                               uint32_t i, const SegTable& S,
+                                                               uint32_t n_segs) {
+    TunnelChainState t;
+    ChainState& st = t.s;
+    st.pa = plan[4 * (size_t)i];
+    st.pb = plan[4 * (size_t)i + 1];
+    t.pc = plan[4 * (size_t)i + 2];
+    st.base = (uint32_t)obase[i];                                 // < need <= out_bytes < 4 GiB
+    st.c = ChainCursor{st.pa.x, 0u};
+    st.hdr = S.fb;
+    st.flat = true;
+    if (st.pb.w & kSegOn) {                     // pkt_len >= payload_off > 0: a segment has bytes
+        Frame s{S.fb, 0u};
+        while (st.c.k < n_segs && (s = S.seg(st.c.k)).len == 0u) ++st.c.k;
+        st.hdr = s.off;
+        st.flat = (st.pa.w & 0xffffu) <= s.len;
+    }
+    return t;
+}
+
+// write_chain_output for the 64-B plan
+template <bool kUdp>
+__device__ __forceinline__ void write_tunnel_chain_output(__amdgpu_buffer_rsrc_t rs, const SegTable& S,
+                                                          uint32_t n_segs, __amdgpu_buffer_rsrc_t ro,
+                                                          uint32_t* __restrict__ out_offsets,
+                                                          uint32_t mss, uint32_t j, uint32_t k,
+                                                          TunnelChainState& t, int lane) {
+    ChainState& st = t.s;
+    const uint32_t fb = S.fb;
+    if (!(st.pb.w & kSegOn)) {                                    // pass-through: a byte copy
+        if (lane == 0) out_offsets[j + 1] = st.base + st.pa.y;
+        chain_copy<false>(rs, S, n_segs, ro, st.c, 0u, st.base, st.pa.y, lane);
+        return;
+    }
+    const SegOut o = seg_out(st.pa, st.pb, mss, k, st.base);
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.po + o.pk;
+    const GatheredHeader G{S, rs, st.pa.x, n_segs, o.po};
+    const uint32_t hdr = st.hdr, d0 = o.d0;
+    const bool flat = st.flat;                                    // wave-uniform
+    auto fetch = [&](uint32_t c) -> uint32_t {
+        return flat ? header_dword(rs, fb, hdr, d0, c) : G.dw((d0 & ~3u) + 4u * c - d0);
+    };
+    const uint32_t hfirst = fetch((uint32_t)lane);
+    // the payload is summed once: for the inner checksum and under the outer one
+    const uint32_t part = chain_copy<true>(rs, S, n_segs, ro, st.c, o.po + o.done, o.d0 + o.po,
+                                           o.pk, lane);
+    const uint32_t pay = be_sum(wave_sum(fold16(part)), o.d0 + o.po);
+    SegPatch Pi[kSegPatches], P[kTunPatches];
+    seg_patches<kUdp>(o, st.pb, k, pay, Pi);
+#pragma unroll
+    for (int u = 0; u < kSegPatches; ++u) P[u] = Pi[u];
+    tunnel_patches(o, st.pb, t.pc, k, pay, P);
+    wave_copy_header_from(ro, o.d0, o.po, hfirst, P, lane, fetch);
+}
+
+template <bool kUdp>
+__global__ __launch_bounds__(kSegBlock)
+void segment_tunnel_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
+                                        const uint32_t* __restrict__ segs, uint32_t n_segs,
+                                        uint32_t n, uint32_t mss, const u32x4* __restrict__ plan,
+                                        const uint32_t* __restrict__ seg_first,
+                                        const uint64_t* __restrict__ obase,
+                                        const uint64_t* __restrict__ totals,
+                                        uint8_t* __restrict__ out, uint32_t out_bytes,
+                                        uint32_t* __restrict__ out_offsets, uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t j0, jend, i;
+    if (!output_run(n, seg_first, totals, out_bytes, out_offsets, out_cap, lane, j0, jend, i)) return;
+    uint32_t cur = seg_first[i], nxt = seg_first[i + 1];
+    const SegTable S{segs, fb};
+    TunnelChainState t = tunnel_chain_state(plan, obase, i, S, n_segs);
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t j = j0; j < jend; ++j) {
+        if (j >= nxt) {                                           // the next chain's first output
+            while (j >= nxt && i + 1u < n) {
+                ++i;
+                cur = nxt;
+                nxt = seg_first[i + 1];
+            }
+            t = tunnel_chain_state(plan, obase, i, S, n_segs);
+        }
+        write_tunnel_chain_output<kUdp>(rs, S, n_segs, ro, out_offsets, mss, j, j - cur, t, lane);
+    }
+}
+
 // the scans and the write's grid, the same for both entries: `n` inputs planned into ws
 template <typename... KArgs, typename... Args>
 int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, uint32_t out_cap,
@@ -812,6 +996,37 @@ int rpkt_gpu_segment_tunnel_batch(const rpkt_batch_t* b, const rpkt_rec_t* outer
                           b->frames_dev, (uint32_t)b->frames_bytes, b->n, mss, ws.plan, seg_first_dev,
                           ws.obase, totals_dev, out_frames_dev, (uint32_t)out_bytes, out_offsets_dev,
                           out_cap);
+}
+
+size_t rpkt_gpu_segment_tunnel_chains_workspace_bytes(uint32_t n) {
+    return seg_ws(nullptr, n, 4).bytes;
+}
+
+int rpkt_gpu_segment_tunnel_chains(const rpkt_chains_t* c, const rpkt_rec_t* outer_dev,
+                                   const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                   uint32_t mss, uint32_t flags, uint8_t* out_frames_dev,
+                                   uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
+                                   uint32_t* seg_first_dev, uint64_t* totals_dev,
+                                   void* workspace_dev, void* stream) {
+    RPKT_TRY(reframe_args_ok(c, outer_dev, mss, flags, RPKT_SEGMENT_UDP, out_frames_dev, out_bytes,
+                             out_offsets_dev, out_cap, seg_first_dev, totals_dev, workspace_dev,
+                             tun_dev, inner_dev));
+    if (c->n_chains == 0) return RPKT_OK;
+
+    const uint32_t n = c->n_chains, fb = (uint32_t)c->buf_bytes;
+    const uint32_t* segs = c->segs_dev;
+    const SegWs ws = seg_ws(workspace_dev, n, 4);
+    const bool udp = (flags & RPKT_SEGMENT_UDP) != 0u;
+    RPKT_TRY(launch(udp ? segment_tunnel_chains_plan_kernel<true>
+                        : segment_tunnel_chains_plan_kernel<false>,
+                    dim3(blocks(n)), dim3(kSegBlock), 0, (hipStream_t)stream, c->buf_dev, fb, segs,
+                    c->n_segs, c->chain_first_dev, n, outer_dev, tun_dev, inner_dev, mss, ws.plan,
+                    seg_first_dev, ws.obase, ws.part));
+    return scan_and_write(udp ? segment_tunnel_chains_write_kernel<true>
+                              : segment_tunnel_chains_write_kernel<false>,
+                          ws, n, out_cap, seg_first_dev, totals_dev, (hipStream_t)stream, c->buf_dev,
+                          fb, segs, c->n_segs, n, mss, ws.plan, seg_first_dev, ws.obase, totals_dev,
+                          out_frames_dev, (uint32_t)out_bytes, out_offsets_dev, out_cap);
 }
 
 }  // extern "C"

@@ -89,6 +89,9 @@ ABI = {
     "rpkt_gpu_segment_tunnel_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_segment_tunnel_batch": (_i, [_B, _p, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32,
                                            _p, _p, _p, _p]),
+    "rpkt_gpu_segment_tunnel_chains_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_segment_tunnel_chains": (_i, [_C, _p, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32,
+                                            _p, _p, _p, _p]),
     "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p, _p]),
@@ -696,6 +699,25 @@ def segment_tunnel_workspace(n, device="cuda"):
     return _workspace("segment_tunnel", n, device)
 
 
+def _segment_tunnel(name, src, what, outer, tun, inner, mss, out_frames, out_offsets, out_cap,
+                    out_bytes, seg_first, totals, workspace, stream, header_max, udp):
+    """segment_tunnel_batch and segment_tunnel_chains: _segment with the three tunnel record
+    tensors and the tunnel bound."""
+    n, fbytes = src.n, src.frames.numel()
+    out_frames, out_bytes, out_offsets, out_cap, seg_first, totals, workspace = _reframe_outputs(
+        what, src, outer, lambda: n + fbytes // mss,
+        lambda cap: fbytes + (cap - n) * (272 if header_max is None else header_max),
+        out_frames, out_offsets, out_cap, out_bytes, seg_first, "seg_first", totals, workspace,
+        "segment_tunnel")
+    if tun.numel() != n * 16 or inner.numel() != n * REC_BYTES:
+        raise RpktError("%s: tunnel or inner records do not fit %d frames" % (what, n))
+    _call(name, ctypes.byref(src.desc()), outer.data_ptr(), tun.data_ptr(), inner.data_ptr(), mss,
+          SEGMENT_UDP if udp else 0, out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(),
+          out_cap, seg_first.data_ptr(), totals.data_ptr(), workspace.data_ptr(),
+          _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
+
+
 def segment_tunnel_batch(batch, outer, tun, inner, mss, out_frames=None, out_offsets=None,
                          out_cap=None, out_bytes=None, seg_first=None, totals=None, workspace=None,
                          stream=None, header_max=None, udp=False):
@@ -710,19 +732,31 @@ def segment_tunnel_batch(batch, outer, tun, inner, mss, out_frames=None, out_off
     32 bytes of extension headers (VXLAN's 8 and GRE's 4..16 are shorter) and the 134 bytes
     segment_batch allows for the inner frame: 268, rounded up to 16; give it for outer IPv6
     extension headers or longer GTP-U extension chains."""
-    n, fbytes = batch.n, batch.frames.numel()
-    out_frames, out_bytes, out_offsets, out_cap, seg_first, totals, workspace = _reframe_outputs(
-        "segment_tunnel_batch", batch, outer, lambda: n + fbytes // mss,
-        lambda cap: fbytes + (cap - n) * (272 if header_max is None else header_max),
-        out_frames, out_offsets, out_cap, out_bytes, seg_first, "seg_first", totals, workspace,
-        "segment_tunnel")
-    if tun.numel() != n * 16 or inner.numel() != n * REC_BYTES:
-        raise RpktError("segment_tunnel_batch: tunnel or inner records do not fit %d frames" % n)
-    _call("rpkt_gpu_segment_tunnel_batch", ctypes.byref(batch.desc()), outer.data_ptr(),
-          tun.data_ptr(), inner.data_ptr(), mss, SEGMENT_UDP if udp else 0, out_frames.data_ptr(),
-          out_bytes, out_offsets.data_ptr(), out_cap, seg_first.data_ptr(), totals.data_ptr(),
-          workspace.data_ptr(), _stream_ptr(stream))
-    return DeviceBatch(out_frames, out_cap, out_offsets), seg_first, totals
+    return _segment_tunnel("rpkt_gpu_segment_tunnel_batch", batch, "segment_tunnel_batch", outer,
+                           tun, inner, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
+                           totals, workspace, stream, header_max, udp)
+
+
+def segment_tunnel_chains_workspace(n, device="cuda"):
+    """The workspace tensor of segment_tunnel_chains for n chains
+    (rpkt_gpu_segment_tunnel_chains_workspace_bytes)."""
+    return _workspace("segment_tunnel_chains", n, device)
+
+
+def segment_tunnel_chains(chains, outer, tun, inner, mss, out_frames=None, out_offsets=None,
+                          out_cap=None, out_bytes=None, seg_first=None, totals=None,
+                          workspace=None, stream=None, header_max=None, udp=False):
+    """rpkt_gpu_segment_tunnel_chains: segment_tunnel_batch over mbuf chains (a DeviceChains),
+    read in place; `outer`, `tun`, `inner` are parse_tunnel_chains' three tensors for them, `udp`
+    and header_max as for segment_tunnel_batch.  The same return value: (out, seg_first, totals),
+    `out` a packed, flat DeviceBatch of wire frames.  The default sizes are
+    segment_tunnel_batch's with the arena's size, chains.buf.numel(), for frames_bytes, which
+    bounds the chains' bytes under segment_chains' condition: no overlapping or shared segments."""
+    if workspace is None:
+        workspace = segment_tunnel_chains_workspace(chains.n, chains.buf.device)
+    return _segment_tunnel("rpkt_gpu_segment_tunnel_chains", chains, "segment_tunnel_chains", outer,
+                           tun, inner, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
+                           totals, workspace, stream, header_max, udp)
 
 
 COALESCE_TRUST_SUMS = 1

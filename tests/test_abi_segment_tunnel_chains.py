@@ -1,0 +1,104 @@
+"""rpkt_gpu_segment_tunnel_chains' argument checks, in the documented order (include/rpkt_gpu.h,
+at enum rpkt_err): rpkt_gpu_segment_chains', with tun_dev and inner_dev required and 16-byte
+aligned along with outer_dev.
+
+CPU only, and skipped where a GPU is visible: the calls carry fake device addresses, so a
+check dropped by mistake must fail at the launch (RPKT_E_HIP, no device) instead of running
+a kernel on them."""
+import ctypes
+
+import pytest
+import torch
+
+from rpkt_amd import engine
+from rpkt_amd.build import build_gpu
+
+pytestmark = pytest.mark.skipif(torch.cuda.is_available(),
+                                reason="fake device addresses: never where a launch could run")
+
+OK, E_INVAL, E_HIP, E_TOO_LARGE, E_ALIGN = 0, -1, -2, -3, -4
+A = 1 << 20                                    # 16-byte aligned, never dereferenced addresses
+REQUIRED = ("outer", "tun", "inner", "out_frames", "out_offsets", "seg_first", "totals", "workspace")
+ADDR = {k: A + (j << 16) for j, k in enumerate(REQUIRED)}
+BUF, SEGS, FIRST = A + (12 << 16), A + (13 << 16), A + (14 << 16)
+
+
+@pytest.fixture(scope="module")
+def fn():
+    build_gpu()
+    return engine.lib().rpkt_gpu_segment_tunnel_chains
+
+
+def chains(n=10, n_segs=20, buf=BUF, buf_bytes=1 << 16, segs=SEGS, first=FIRST):
+    return engine.Chains(buf, buf_bytes, segs, first, n_segs, n)
+
+
+def call(fn, c, mss=1448, flags=0, out_bytes=1 << 16, out_cap=64, **ptr):
+    p = dict(ADDR, **ptr)
+    return fn(ctypes.byref(c) if c is not None else None, p["outer"], p["tun"], p["inner"], mss,
+              flags, p["out_frames"], out_bytes, p["out_offsets"], out_cap, p["seg_first"],
+              p["totals"], p["workspace"], None)
+
+
+def test_the_entry_is_exported_and_sized(fn):
+    L = engine.lib()
+    assert {"rpkt_gpu_segment_tunnel_chains",
+            "rpkt_gpu_segment_tunnel_chains_workspace_bytes"} <= set(engine.EXPORTS)
+    ws = L.rpkt_gpu_segment_tunnel_chains_workspace_bytes
+    assert ws(0) == 0
+    # the flat tunnel entry's workspace per chain: a 64-byte plan where segment_chains has 32
+    for n in (1, 255, 256, 257, 70000):
+        assert ws(n) % 16 == 0 and ws(n) == L.rpkt_gpu_segment_tunnel_workspace_bytes(n)
+        assert ws(n) == L.rpkt_gpu_segment_chains_workspace_bytes(n) + 32 * n
+
+
+def test_argument_checks_in_the_documented_order(fn):
+    """One case per check; each also breaks a later check, which must not be the one
+    reported."""
+    # 1. NULL chains / a record array / a required output / workspace, before the flags
+    assert call(fn, None, flags=1) == E_INVAL
+    for k in REQUIRED:
+        assert call(fn, chains(n=0), flags=1, **{k: None}) == E_INVAL, k
+        assert call(fn, chains(n=0), **{k: None}) == E_INVAL, k     # even for no chains
+    # 2. flags (0 or RPKT_SEGMENT_UDP), then mss: before n_chains == 0
+    for bad in (1, 2, 17, 32, 0x80000000):
+        assert call(fn, chains(n=0), flags=bad) == E_INVAL
+    for flags in (0, 16):
+        for mss in (0, 65536, 0xffffffff):
+            assert call(fn, chains(n=0), mss=mss, flags=flags) == E_INVAL
+        for mss in (1, 65535):
+            assert call(fn, chains(n=0), mss=mss, flags=flags) == OK
+    # 3. n_chains == 0: RPKT_OK, nothing else is looked at
+    assert call(fn, chains(n=0, buf=None, segs=None, first=None, buf_bytes=1 << 33,
+                           n_segs=0xffffffff), out_cap=0, out_bytes=1 << 33, outer=A + 1,
+                tun=A + 2, inner=A + 3, totals=A + 4) == OK
+    # 4. the chains: NULL chain_first_dev, or with segments a NULL buf_dev / segs_dev, before
+    #    the sizes; then buf_bytes and n_segs
+    assert call(fn, chains(first=None, buf_bytes=1 << 32)) == E_INVAL
+    assert call(fn, chains(buf=None, buf_bytes=1 << 32)) == E_INVAL
+    assert call(fn, chains(segs=None, n_segs=0x80000000)) == E_INVAL
+    assert call(fn, chains(buf_bytes=1 << 32), out_bytes=1 << 32, out_cap=0) == E_TOO_LARGE
+    assert call(fn, chains(buf_bytes=0xffffff01), out_cap=0) == E_TOO_LARGE
+    assert call(fn, chains(n_segs=0x80000000), out_cap=0) == E_TOO_LARGE
+    # 5. out_bytes, at the same limit, before out_cap
+    assert call(fn, chains(), out_bytes=1 << 32, out_cap=0) == E_TOO_LARGE
+    assert call(fn, chains(), out_bytes=0xffffff01, out_cap=0) == E_TOO_LARGE
+    # 6. out_cap == 0, before the alignment
+    assert call(fn, chains(), out_cap=0, outer=ADDR["outer"] + 8) == E_INVAL
+    assert call(fn, chains(), out_cap=0, tun=ADDR["tun"] + 8) == E_INVAL
+    assert call(fn, chains(segs=SEGS + 4), out_cap=0) == E_INVAL
+    # 7. alignment: segs and totals 8 B; the three record arrays, out_frames, workspace 16 B
+    assert call(fn, chains(segs=SEGS + 4)) == E_ALIGN
+    assert call(fn, chains(), totals=ADDR["totals"] + 4) == E_ALIGN
+    for k in ("outer", "tun", "inner", "out_frames", "workspace"):
+        assert call(fn, chains(), **{k: ADDR[k] + 8}) == E_ALIGN, k
+    assert call(fn, chains(segs=SEGS + 8), totals=ADDR["totals"] + 8) == E_HIP   # a launch
+
+
+def test_the_limits_are_accepted(fn):
+    """The largest sizes pass the checks (and fail only at the launch: no device here);
+    chains without segments need neither an arena nor a segment table."""
+    assert call(fn, chains(buf_bytes=0xffffff00, n_segs=0x7fffffff), out_bytes=0xffffff00,
+                out_cap=0xffffffff, flags=16) == E_HIP
+    assert call(fn, chains(n_segs=0, buf=None, segs=None), mss=1) == E_HIP
+    assert call(fn, chains(n=0xffffffff), mss=65535) == E_HIP

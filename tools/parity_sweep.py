@@ -26,7 +26,10 @@ rpkt_gpu_coalesce_tunnel_batch with random flags against tests/coalesce_tunnel_m
 random cuts) through the tunnel parse over chains against tests/tunnel_chain_model.py; (d)
 a nested tunnel batch (tests/nested_tunnel_ref.py's recipe: config 13 / 14 frames, frame k
 wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level passes
-(rpkt_gpu_parse_tunnel_next, records and flow events) against the oracle composition.  Build and forward rewrite frames in place, so they run on generator batches
+(rpkt_gpu_parse_tunnel_next, records and flow events) against the oracle composition; (e) a
+fuzzed tunnel chain batch (config 13 / 14) through rpkt_gpu_segment_tunnel_chains at a random mss
+and flag, with the chain tunnel parse's records or the flat ones of the flattened bytes, against
+tests/segment_tunnel_chains_model.py.  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -50,6 +53,7 @@ import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
 import segment_chains_model  # noqa: E402
 import segment_model  # noqa: E402
+import segment_tunnel_chains_model  # noqa: E402
 import segment_tunnel_model  # noqa: E402
 import tunnel_chain_model  # noqa: E402
 import tunnel_frames  # noqa: E402
@@ -370,6 +374,29 @@ def check_tunnel_next(rng, seed):
     return {"cfg": cfg, "n": int(hb.n), "flags": flags}
 
 
+def check_segment_tunnel_chains(rng, seed):
+    """rpkt_gpu_segment_tunnel_chains on config 13 / 14 chains in the fuzz layout at a random
+    mss, with or without RPKT_SEGMENT_UDP, against tests/segment_tunnel_chains_model.py."""
+    import torch
+    cfg = int(rng.choice([13, 14]))
+    hc = gen.make_chains(cfg, n=int(rng.integers(1, 3000)), layout="fuzz", seed=seed)
+    mss = int(rng.choice([7, 16, 17, 100, 300, 536, 1448, 65535]))
+    udp = bool(rng.random() < 0.5)
+    kind = "chain" if rng.random() < 0.6 else "flat"
+    recs = segment_tunnel_chains_model.RECORDS[kind](hc)
+    out, first, totals = segment_tunnel_chains_model.segment(hc, *recs, mss, udp)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    d = [torch.from_numpy(np.ascontiguousarray(r).view(np.uint8).copy()).cuda() for r in recs]
+    odb, gs, gt = engine.segment_tunnel_chains(engine.DeviceChains.from_host(hc), *d, mss,
+                                               out_cap=out_cap,
+                                               out_bytes=int(totals[1]) + int(rng.integers(0, 40)),
+                                               udp=udp)
+    same_reframed("segment_tunnel_chains", odb, gs, gt, out, first, totals, out_cap)
+    kinds = segment_tunnel_model.cut_kinds(first, recs[1])
+    return {"cfg": cfg, "n": int(hc.n), "mss": mss, "udp": udp, "records": kind,
+            "n_out": int(totals[0]), "cut": [kinds[k] for k in (0, 1, 2, 3)]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=8.0)
@@ -406,6 +433,8 @@ def main():
                 rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
                 step = "tunnel_next"
                 rec["tunnel_next"] = check_tunnel_next(rng, seed)
+                step = "segment_tunnel_chains"
+                rec["segment_tunnel_chains"] = check_segment_tunnel_chains(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")

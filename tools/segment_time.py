@@ -47,7 +47,19 @@ inner frames and the device copy: `tunnel_over_tcp_per_output_byte` (the times o
 frame bytes), `tunnel_over_tcp_per_byte` and `tunnel_over_copy_per_byte` (over the bytes
 moved) are same-run ratios.  Its output is checked by a tunnel parse with both sums: 23
 segments a frame, every one decoded with valid outer and inner IPv4, UDP and TCP sums.  With
---trace-launches the traced calls are the tunnel entry's."""
+--trace-launches the traced calls are the tunnel entry's.
+
+    python tools/segment_time.py --tunnel-chains [--out profiles/segment/tunnel_chains/times.json]
+
+adds rpkt_gpu_segment_tunnel_chains on the --tunnel workload's VXLAN super-frames as mbuf chains
+in the --chains layout (17 segments a chain, the last one 104 B), the records from
+rpkt_gpu_parse_tunnel_chains, in the same interleaved rounds as every leg of --tunnel and
+--chains and a device copy of the tunnelled frames' bytes.  The chains' output must equal the
+flat tunnel entry's, byte for byte.  `tunnel_chains_over_flatten_then_segment_tunnel` is
+t(segment_tunnel_chains) / (t(segment_tunnel_batch) + t(device copy of the same bytes)): what a
+caller without the entry must do; `tunnel_chains_over_chains_per_output_byte` is against
+rpkt_gpu_segment_chains on the un-tunnelled chains, the chain-side twin of
+`tunnel_over_tcp_per_output_byte`."""
 import argparse
 import json
 import os
@@ -131,10 +143,9 @@ def vxlan_prefix():
 ROOM, HEADROOM = 2048, 128                                        # gen.MBUF_ROOM, MBUF_HEADROOM
 
 
-def mbuf_chains(torch, engine, db, n, seed):
-    """The frames of the strided device batch `db` as DeviceChains in the mbuf layout, built
-    on the device."""
-    flen = HDR + PAYLOAD
+def mbuf_chains(torch, engine, db, n, seed, flen=HDR + PAYLOAD):
+    """The `flen`-byte frames of the strided device batch `db` as DeviceChains in the mbuf
+    layout, built on the device."""
     per = -(-flen // ROOM)
     rows = torch.zeros((n, per * ROOM), dtype=torch.uint8, device="cuda")
     rows[:, :flen] = db.frames.view(n, flen)
@@ -185,13 +196,18 @@ def main():
                     help="also time RPKT_SEGMENT_UDP on the same workload as UDP datagrams")
     ap.add_argument("--tunnel", action="store_true",
                     help="also time rpkt_gpu_segment_tunnel_batch on the same frames behind VXLAN")
+    ap.add_argument("--tunnel-chains", action="store_true",
+                    help="also time rpkt_gpu_segment_tunnel_chains on the VXLAN frames as mbuf "
+                         "chains (implies --tunnel and --chains)")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-launches", type=int, default=0,
                     help="no timing: this many calls, for a kernel-trace pass")
     a = ap.parse_args()
-    a.out = a.out or ("profiles/segment/tunnel_times.json" if a.tunnel else
+    a.tunnel, a.chains = a.tunnel or a.tunnel_chains, a.chains or a.tunnel_chains
+    a.out = a.out or ("profiles/segment/tunnel_chains/times.json" if a.tunnel_chains else
+                      "profiles/segment/tunnel_times.json" if a.tunnel else
                       "profiles/udp_reframe/segment_times.json" if a.udp else
                       "profiles/segment_chains/times.json" if a.chains else "profiles/segment/times.json")
     import torch
@@ -274,9 +290,29 @@ def main():
                                         totals=tun_totals, workspace=tws, stream=stream)
 
         legs = {"segment_tunnel": segment_tunnel, **legs}
+    if a.tunnel_chains:
+        tdcs = [mbuf_chains(torch, engine, db, n, seed, tlen) for db, seed in zip(tdbs, (19, 1919))]
+        tcrecs = [engine.parse_tunnel_chains(dc, 0) for dc in tdcs]
+        assert all(torch.equal(x, y) for c, f in zip(tcrecs, trecs) for x, y in zip(c, f))
+        tc_out = torch.empty(tneed, dtype=torch.uint8, device="cuda")
+        tc_offsets, tc_first = torch.empty_like(out_offsets), torch.empty_like(seg_first)
+        tc_totals = torch.zeros_like(totals)
+        tcws = engine.segment_tunnel_chains_workspace(n)
+
+        def segment_tunnel_chains(k):
+            engine.segment_tunnel_chains(tdcs[k % R], *tcrecs[k % R], MSS, out_frames=tc_out,
+                                         out_offsets=tc_offsets, seg_first=tc_first,
+                                         totals=tc_totals, workspace=tcws, stream=stream)
+
+        def copy_tunnel(k):
+            tun_out[:n * tlen].copy_(tdbs[k % R].frames)
+
+        legs = {"segment_tunnel_chains": segment_tunnel_chains, **legs,
+                "device_copy_tunnel": copy_tunnel}
     if a.trace_launches:
         for k in range(a.trace_launches):
-            (segment_tunnel if a.tunnel else segment_chains if a.chains else segment)(k)
+            (segment_tunnel_chains if a.tunnel_chains else segment_tunnel if a.tunnel else
+             segment_chains if a.chains else segment)(k)
         torch.cuda.synchronize()
         return
     med, ms = time_legs(torch, stream, legs, a.launches, a.rounds)
@@ -327,6 +363,12 @@ def main():
         assert (ti["payload_len"][~last] == MSS).all()
         assert (ti["payload_len"][last] == PAYLOAD - (per - 1) * MSS).all()
 
+    if a.tunnel_chains:                                           # the same output from the chains
+        segment_tunnel_chains(0)
+        torch.cuda.synchronize()
+        assert torch.equal(tc_totals, tun_totals) and torch.equal(tc_first, tun_first)
+        assert torch.equal(tc_offsets, tun_offsets) and torch.equal(tc_out, tun_out)
+
     moved = {"frames_in": n * flen, "records_in": n * 80, "frames_out": need,
              "offsets_out": (n_out + 1) * 4}
     alg = sum(moved.values())
@@ -375,6 +417,23 @@ def main():
             (med["segment_tunnel"] / talg) / (med["segment_batch"] / alg), 4)
         res["tunnel_over_copy_per_byte"] = round(
             (med["segment_tunnel"] / talg) / (med["device_copy"] / (2 * n * flen)), 4)
+    if a.tunnel_chains:
+        tn_segs = tdcs[0].segs.numel() // 2
+        res["tunnel_chains"] = {"room": ROOM, "slot": ROOM + HEADROOM, "segments": tn_segs,
+                                "arena_bytes": tdcs[0].buf.numel()}
+        tcalg = talg + tn_segs * 8 + (n + 1) * 4
+        res["ms"]["segment_tunnel_chains"]["bytes"] = tcalg
+        res["ms"]["segment_tunnel_chains"]["fraction_of_8TBs"] = round(
+            tcalg / (med["segment_tunnel_chains"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        res["ms"]["device_copy_tunnel"]["bytes"] = 2 * n * tlen
+        res["ms"]["device_copy_tunnel"]["fraction_of_8TBs"] = round(
+            2 * n * tlen / (med["device_copy_tunnel"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        res["tunnel_chains_over_flatten_then_segment_tunnel"] = round(
+            med["segment_tunnel_chains"] / (med["segment_tunnel"] + med["device_copy_tunnel"]), 4)
+        res["tunnel_chains_over_chains_per_output_byte"] = round(
+            (med["segment_tunnel_chains"] / tneed) / (med["segment_chains"] / need), 4)
+        res["tunnel_chains_over_segment_tunnel"] = round(
+            med["segment_tunnel_chains"] / med["segment_tunnel"], 4)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
