@@ -77,6 +77,8 @@ pub const RPKT_COALESCE_TRUST_SUMS: u32 = 1;
 pub const RPKT_COALESCE_UDP: u32 = 16;
 /// rpkt_gpu_segment_batch, rpkt_gpu_segment_chains: also segment UDP datagrams
 pub const RPKT_SEGMENT_UDP: u32 = 16;
+/// rpkt_gpu_fragment_batch: cut IPv4 packets that have DF set, too
+pub const RPKT_FRAGMENT_IGNORE_DF: u32 = 1;
 
 // enum rpkt_opt_stop / rpkt_layer_stop
 pub const RPKT_OPT_NONE: u8 = 0;
@@ -427,6 +429,18 @@ extern "C" {
                                           out_bytes: u64, out_offsets_dev: *mut u32, out_cap: u32,
                                           seg_first_dev: *mut u32, totals_dev: *mut u64,
                                           workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_fragment_batch for n input frames.
+    pub fn rpkt_gpu_fragment_workspace_bytes(n: u32) -> usize;
+    /// IPv4 / IPv6 fragmentation on the device: each IP packet longer than the L3 MTU `mtu` is
+    /// cut into fragments (RFC 791 with the Linux option rule; RFC 8200 section 4.5 with
+    /// identification `ip6_ident` + the frame's index), every other frame copied; the output
+    /// is a packed batch of `out_cap` slots.
+    pub fn rpkt_gpu_fragment_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
+                                   mtu: u32, flags: u32, ip6_ident: u32,
+                                   out_frames_dev: *mut u8, out_bytes: u64,
+                                   out_offsets_dev: *mut u32, out_cap: u32,
+                                   frag_first_dev: *mut u32, totals_dev: *mut u64,
+                                   workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
     /// Workspace of rpkt_gpu_coalesce_batch for n positions.
     pub fn rpkt_gpu_coalesce_workspace_bytes(n: u32) -> usize;
     /// TCP receive coalescing (GRO / LRO) on the device: consecutive in-order TCP segments of

@@ -547,6 +547,28 @@ pub unsafe fn segment_tunnel_chains(chains: &ffi::rpkt_chains_t, outer_dev: *con
                                               workspace_dev, stream))
 }
 
+/// rpkt_gpu_fragment_workspace_bytes: the workspace of fragment_batch for `n` input frames.
+pub fn fragment_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_fragment_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_fragment_batch: IPv4 / IPv6 fragmentation of a parsed batch at the L3 MTU `mtu`
+/// (1..65535).  `flags`: 0, or `ffi::RPKT_FRAGMENT_IGNORE_DF` to cut IPv4 packets that have DF
+/// set, too; `ip6_ident` + i is the identification in frame i's IPv6 Fragment headers.  `out`
+/// is laid out as segment_batch's, with `seg_first_dev` the first fragment of every input frame.
+///
+/// # Safety
+/// As for `segment_batch`, with `workspace_dev` holding `fragment_workspace_bytes(batch.n)`
+/// bytes (16-byte aligned).
+pub unsafe fn fragment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mtu: u32,
+                             flags: u32, ip6_ident: u32, out: &SegmentOut,
+                             workspace_dev: *mut core::ffi::c_void,
+                             stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_fragment_batch(batch, recs_dev, mtu, flags, ip6_ident, out.frames_dev,
+                                       out.out_bytes, out.offsets_dev, out.out_cap,
+                                       out.seg_first_dev, out.totals_dev, workspace_dev, stream))
+}
+
 /// The outputs of rpkt_gpu_coalesce_batch: a packed batch of `out_cap` slots (`frames_dev`,
 /// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first
 /// position of every output (`src_first_dev`, `n + 1` entries), each merged output's segment

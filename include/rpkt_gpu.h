@@ -116,6 +116,9 @@ enum rpkt_status {
  *     inner_dev in recs_dev's places: each required (E_INVAL) and 16-byte aligned (E_ALIGN);
  *   rpkt_gpu_segment_tunnel_chains: rpkt_gpu_segment_chains' order with the same three in
  *     recs_dev's places;
+ *   rpkt_gpu_fragment_batch: rpkt_gpu_segment_batch's order with frag_first_dev in
+ *     seg_first_dev's place, flags other than 0 or RPKT_FRAGMENT_IGNORE_DF, then mtu outside
+ *     1..65535 in mss's place;
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
@@ -788,7 +791,8 @@ int rpkt_gpu_forward_batch(const rpkt_batch_t* batch, const rpkt_fwd_t* fwd, uin
  * A tunnelled frame is to this entry what its outer record says: it passes through, and with
  * RPKT_SEGMENT_UDP the OUTER datagram of a VXLAN / GTP-U frame would be cut, which destroys the
  * tunnel; rpkt_gpu_segment_tunnel_batch (below) cuts the inner TCP or UDP instead.
- * Not covered: a segment size per flow, IPv4 UDP fragmentation (UFO). */
+ * Not covered: a segment size per flow.  (IPv4 UDP fragmentation, UFO, is
+ * rpkt_gpu_fragment_batch below: another contract, one datagram in many IP fragments.) */
 #define RPKT_SEGMENT_UDP  16u   /* also segment UDP datagrams (flags of both segment entries) */
 
 size_t rpkt_gpu_segment_workspace_bytes(uint32_t n);
@@ -949,6 +953,111 @@ int rpkt_gpu_segment_tunnel_chains(const rpkt_chains_t* chains, const rpkt_rec_t
                                    uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
                                    uint32_t* seg_first_dev, uint64_t* totals_dev,
                                    void* workspace_dev, void* stream);
+
+/* ---- IPv4 / IPv6 fragmentation ---------------------------------------------------- */
+
+/* What makes a frame fit a link: rpkt_gpu_build_tunnel_batch puts 50 bytes or more of outer
+ * headers around a frame that was MTU-sized already, and a UDP datagram without UDP_SEGMENT, an
+ * ICMP message or any other IP packet larger than the MTU has no other way onto the wire
+ * (RPKT_SEGMENT_UDP re-frames a datagram into several datagrams, a different contract).
+ * rpkt_gpu_fragment_batch cuts IP packets into fragments on the device: IPv4 under RFC 791
+ * and the Linux ip_do_fragment slow path with ip_options_fragment, IPv6 under RFC 8200
+ * section 4.5.  The fragments are what rpkt_gpu_parse_batch reads: ip_frag in the record,
+ * RPKT_S_IP6_FRAGMENT, the Fragment header among the extension headers it walks.  The output
+ * is the complete transmit batch, in input order: every input frame yields one output frame or
+ * more, and a frame that is not cut passes through as a byte copy of [0, frame_len), exactly as
+ * in rpkt_gpu_segment_batch.
+ *
+ * mtu: 1..65535, the L3 MTU: the largest IP packet, its IP header included; one serves the
+ * call.  flags: 0 or RPKT_FRAGMENT_IGNORE_DF.  recs_dev: the records of a parse of this same
+ * batch (RPKT_F_IPV6 for IPv6 frames to be cut; the sum flags do not matter).  They only locate
+ * things -- status, the dispatch ethertype, l3_off, l4_off -- and every header byte is read
+ * from the frame.  Below l3 = l3_off, l4 = l4_off.
+ *
+ * IPv4.  With ihl (the low nibble of byte l3, times 4) and L (be16 at l3 + 2) from the frame,
+ * frame i is cut iff all of these hold:
+ *   - the dispatch ethertype is 0x0800 and status is one under which the IPv4 header parsed:
+ *     OK, L4_OTHER, UDP_SHORT, UDP_BAD_LEN, TCP_SHORT, TCP_BAD_DOFF, ICMP_EMPTY;
+ *   - l4 == l3 + ihl, ihl in 20..60;
+ *   - l3 + L <= frame_len;
+ *   - L > mtu;
+ *   - DF (0x4000 of the frag word, be16 at l3 + 6) is clear, or RPKT_FRAGMENT_IGNORE_DF is set;
+ *   - c = (mtu - ihl) & ~7 is at least 8;
+ *   - with P = L - ihl, n_i = ceil(P / c) and o the frame's own 13-bit offset,
+ *     o + (n_i - 1) * c / 8 <= 0x1fff.
+ * A frame that is itself a fragment is cut again like any other, as a router does.  Fragment k
+ * carries p_k = c bytes, the last one p_last = P - (n_i - 1) * c:
+ *   bytes      [0, l4) of the frame, then [l4 + k * c, + p_k); bytes after the IP packet's end
+ *              (Ethernet padding) are not carried;
+ *   packet_len ihl + p_k; ident, tos, ttl, protocol and the addresses are copied;
+ *   frag word  (o + k * c / 8) | MF, MF (0x2000) on every fragment but the last, and on the last
+ *              too when the input had MF; the reserved bit and DF are written as 0, as Linux
+ *              rebuilds frag_off (a DF frame is only ever cut under RPKT_FRAGMENT_IGNORE_DF);
+ *   options    fragment 0 keeps them all.  In fragments k > 0 they are rewritten exactly as
+ *              ip_options_fragment does it: walk from byte 20; an EOL (type 0) ends the walk; a
+ *              NOOP (type 1) advances by one byte; otherwise the option's length is its byte
+ *              1, and a length below 2 or past the header's end ends the walk; an option whose
+ *              type has bit 0x80 (copied) clear has all its bytes overwritten with 0x01.  ihl
+ *              does not change;
+ *   checksum   the header checksum filled as RPKT_BUILD_IP_CSUM fills it;
+ *   L4 bytes   untouched: a filled UDP checksum stays what it was, over the whole datagram,
+ *              which is UFO.
+ *
+ * IPv6.  Frame i is eligible iff the dispatch ethertype is 0x86DD (so the records were parsed
+ * with RPKT_F_IPV6) and status is OK, L4_OTHER, UDP_SHORT, UDP_BAD_LEN, TCP_SHORT or
+ * TCP_BAD_DOFF.  The extension headers are walked in the frame from x = l3 + 40 with the fixed
+ * header's next_header, at most RPKT_MAX_IP6_EXT of them and while x < l4: types 0, 43 and 60
+ * are 8 * (1 + byte x+1) long, type 51 is 4 * (2 + byte x+1); a type 44 anywhere makes the whole
+ * frame pass through (it is a fragment or an atomic fragment already, and IPv6 is fragmented at
+ * its source only); any other type ends the walk; a header that runs past l4 makes the frame pass
+ * through.  U, the end of the per-fragment headers (RFC 8200: the headers every node on the
+ * path looks at), is the end of the last Routing header met; without one the end of a
+ * Hop-by-Hop header when that is the first header; otherwise l3 + 40.  With plen the fixed
+ * header's payload_len (be16 at l3 + 4), E = l3 + 40 + plen and F = E - U, the frame is cut iff
+ * l3 + 40 <= l4 <= E <= frame_len, 40 + plen > mtu, and c = (mtu - (U - l3) - 8) & ~7 is at
+ * least 8.  It yields n_i = ceil(F / c) fragments; fragment k carries p_k = c bytes, the last
+ * one the rest:
+ *   bytes        [0, U) of the frame, an 8-byte Fragment header, then [U + k * c, + p_k);
+ *   payload_len  (U - l3 - 40) + 8 + p_k;
+ *   next header  the next-header byte of the last per-fragment header (byte l3 + 6 when there
+ *                is none) becomes 44, and its old value the Fragment header's next_header;
+ *   Fragment     byte 0 that next_header, byte 1 0, bytes 2..3 be16 (k * c) | (k < n_i - 1),
+ *                bytes 4..7 be32 ip6_ident + i (mod 2^32; i the input frame's index).
+ *
+ * frag_first_dev, totals_dev, out_frames_dev, out_bytes, out_offsets_dev and out_cap are
+ * rpkt_gpu_segment_batch's seg_first_dev, totals_dev (u64[2] = {n_out, out_bytes_needed}),
+ * out_frames_dev, out_bytes, out_offsets_dev and out_cap word for word: the outputs of frame i
+ * are [frag_first[i], frag_first[i+1]); the true offsets and the spare slots that equal
+ * out_bytes_needed when the batch fits; on overflow frag_first_dev and totals_dev still exact
+ * and the rest unspecified; nothing ever written outside [out_frames_dev, + out_bytes) and
+ * out_offsets_dev[0..out_cap].
+ * Bounds for sizing: every cut has c >= 8 and c >= cmin = (mtu - A - 8) & ~7, A the longest
+ * per-fragment L3 header of the batch (ihl; U - l3), so n_out <= n + floor(frames_bytes /
+ * max(8, cmin)); out_bytes_needed <= frames_bytes + (n_out - n) * H, H the longest l4_off
+ * (IPv4) or U + 8 (IPv6) of the batch.
+ * workspace_dev: rpkt_gpu_fragment_workspace_bytes(n) bytes, 16-byte aligned; calls that share
+ * one must be ordered (one stream).  The call is plan, prefix sums and write on `stream` with
+ * no host step: rpkt_gpu_parse_batch -> rpkt_gpu_fragment_batch -> rpkt_gpu_parse_batch over
+ * out_cap slots captures as one graph.
+ * The records must come from a parse of the same batch.  With other records the outputs are
+ * unspecified, but every frame byte is read through the bounds-checked buffer resource and
+ * every byte written through the one over the output, and a record whose offsets do not nest as
+ * above makes the frame pass through: wrong frames, never a fault.
+ * A tunnelled frame is to this entry what its outer record says: the OUTER IP packet is
+ * fragmented, which is what a VTEP does with an encapsulation that is over the MTU.
+ * Argument checks: rpkt_gpu_segment_batch's in its order (at enum rpkt_err).
+ * Not covered: reassembly (the receive-side inverse: a match across frames on source,
+ * destination, protocol and identification); fragmentation over mbuf chains; fragmenting the
+ * inner packet of a tunnel; an MTU per frame. */
+#define RPKT_FRAGMENT_IGNORE_DF 1u   /* cut IPv4 packets that have DF set, too */
+
+size_t rpkt_gpu_fragment_workspace_bytes(uint32_t n);
+int rpkt_gpu_fragment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev, uint32_t mtu,
+                            uint32_t flags, uint32_t ip6_ident,
+                            uint8_t* out_frames_dev, uint64_t out_bytes,
+                            uint32_t* out_offsets_dev, uint32_t out_cap,
+                            uint32_t* frag_first_dev, uint64_t* totals_dev,
+                            void* workspace_dev, void* stream);
 
 /* ---- TCP and UDP receive coalescing (GRO / LRO, UDP GRO) --------------------------- */
 

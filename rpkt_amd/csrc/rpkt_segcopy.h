@@ -1,9 +1,11 @@
-// rpkt_segcopy.h — what the two units that re-frame a batch share (rpkt_segment.hip: one
-// frame into many; rpkt_coalesce.hip: many into one).  Host: the entries' argument checks and
-// the carving of their workspaces.  Device: what a record says about a TCP or UDP frame, a
+// rpkt_segcopy.h — what the units that re-frame a batch share (rpkt_segment.hip and
+// rpkt_fragment.hip: one frame into many; rpkt_coalesce.hip: many into one).  Host: the
+// entries' argument checks, the carving of their workspaces and, for the two that cut, the
+// launch of the scans and the write.  Device: what a record says about a TCP or UDP frame, a
 // tile's records staged through LDS, header sums by one lane, the block scans of the plan ->
-// scan -> write structure, and the wave copy between any two byte phases that sums what it
-// copies.
+// scan -> write structure, the end of a plan kernel and the start of a write kernel's wave
+// (its run of outputs and their input frame), and the wave copy between any two byte phases
+// that sums what it copies.
 // Everything is inline in an anonymous namespace.
 #pragma once
 #include "rpkt_common.h"
@@ -69,6 +71,24 @@ struct Carve {
     }
     size_t used() const { return (size_t)(at - base); }
 };
+
+// the workspace: per-frame plans (32 B: `quads` 2; the tunnel entry's 64 B: 4), per-frame
+// output byte bases (u64), block sums (count, bytes: u64 pairs)
+struct SegWs {
+    u32x4*    plan;
+    uint64_t* obase;
+    uint64_t* part;
+    size_t    bytes;
+};
+inline SegWs seg_ws(void* ws, uint32_t n, uint32_t quads = 2) {
+    Carve c(ws);
+    SegWs w;
+    w.plan = c.take<u32x4>(quads * (size_t)n);
+    w.obase = c.take<uint64_t>(n);
+    w.part = c.take<uint64_t>(2 * (size_t)blocks(n));
+    w.bytes = c.used();
+    return w;
+}
 
 // What the record's dwords 0, 5, 7, 8, 16, 17 say about a frame of `len` bytes: `on`, status
 // OK and an unfragmented TCP packet (or, with `with_udp`, UDP datagram: `udp`) over IPv4 or
@@ -208,6 +228,23 @@ __device__ __forceinline__ void block_sums_to_part(uint64_t cnt, uint64_t bytes,
     }
 }
 
+// The plan's end: frame i's plan (words 0..7 of its kQuads * 16 bytes), count and bytes to the
+// workspace, the block's sums to part.
+template <int kQuads = 2>
+__device__ __forceinline__ void plan_store(bool valid, uint32_t i, const uint32_t (&p)[8],
+                                           uint64_t cnt, uint64_t bytes, u32x4* __restrict__ plan,
+                                           uint32_t* __restrict__ seg_first,
+                                           uint64_t* __restrict__ obase, uint64_t* __restrict__ part,
+                                           uint64_t* red) {
+    if (valid) {
+        plan[kQuads * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
+        plan[kQuads * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
+        seg_first[i] = (uint32_t)cnt;
+        obase[i] = bytes;
+    }
+    block_sums_to_part(cnt, bytes, part, red);
+}
+
 // one block: the nb block sums -> their exclusive prefixes, kSegBlock at a time with a carry;
 // the totals, and the total count as a u32 to `count` unless that is null
 __global__ __launch_bounds__(kSegBlock)
@@ -231,6 +268,23 @@ void scan_parts_kernel(uint64_t* __restrict__ part, uint32_t nb, uint64_t* __res
         totals[0] = ca;
         totals[1] = cb;
         if (count) *count = (uint32_t)ca;
+    }
+}
+
+// after scan_parts_kernel over the block sums, which also stores seg_first[n]:
+// one block per kSegBlock frames: counts and bytes -> seg_first and the output byte bases
+__attribute__((unused))          // rpkt_coalesce.hip places its outputs with a scan of its own
+__global__ __launch_bounds__(kSegBlock)
+void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
+                                uint32_t* __restrict__ seg_first, uint64_t* __restrict__ obase) {
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
+    uint64_t a = i < n ? seg_first[i] : 0, b = i < n ? obase[i] : 0;
+    uint64_t ta, tb;
+    block_excl_scan2(a, b, ta, tb, red);
+    if (i < n) {
+        seg_first[i] = (uint32_t)(part[2 * (size_t)blockIdx.x] + a);
+        obase[i] = part[2 * (size_t)blockIdx.x + 1] + b;
     }
 }
 
@@ -388,6 +442,66 @@ struct SegOut {
     bool v6, last;
     uint32_t l3, l4, po, done, pk, d0;
 };
+
+// A wave writes kSegRun consecutive outputs.  What precedes an output's first copy load is a
+// chain of dependent loads (the totals, the search, the plan), microseconds against the
+// fraction of one that 1.5 KB take to copy; with one output a wave that chain bounded the
+// kernel at 0.55 of the same bytes' device copy.  Here the search is done once for the run,
+// and the outputs after the first find their frame by stepping along seg_first.
+#ifndef RPKT_SEG_RUN
+#define RPKT_SEG_RUN 8
+#endif
+constexpr uint32_t kSegRun = RPKT_SEG_RUN;
+
+// The wave's run of outputs [j0, jend) and the input frame i of output j0; false when the
+// wave has nothing to write (past out_cap, an overflowing batch, only spare slots, whose
+// offsets it fills).  Wave-uniform throughout.
+__device__ __forceinline__ bool output_run(uint32_t n, const uint32_t* __restrict__ seg_first,
+                                           const uint64_t* __restrict__ totals, uint32_t out_bytes,
+                                           uint32_t* __restrict__ out_offsets, uint32_t out_cap,
+                                           int lane, uint32_t& j0, uint32_t& jend, uint32_t& i) {
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t j64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kSegRun;
+    if (j64 >= out_cap) return false;
+    j0 = (uint32_t)j64;
+    const uint32_t j1 = out_cap - j0 < kSegRun ? out_cap : j0 + kSegRun;   // outputs [j0, j1)
+    const uint64_t n_out = totals[0], need = totals[1];
+    if (n_out > out_cap || need > out_bytes) return false;        // overflow: the totals say so
+    // spare slots are empty frames at the end
+    if ((uint32_t)lane < j1 - j0 && j0 + (uint32_t)lane >= n_out)
+        out_offsets[j0 + (uint32_t)lane + 1u] = (uint32_t)need;
+    if (j0 >= n_out) return false;
+    if (j0 == 0u && lane == 0) out_offsets[0] = 0u;
+    // the input frame of output j0: the last i with seg_first[i] <= j0 (every frame has an
+    // output, so i <= j0).  64 probes a round, one per lane: three dependent loads at
+    // n = 32,768 where a binary search has fifteen.
+    uint32_t lo = 0, hi = j0 < n - 1u ? j0 : n - 1u;
+    while (lo < hi) {
+        const uint32_t step = (hi - lo) / kWave + 1u;
+        const uint64_t at = (uint64_t)lo + (uint64_t)(lane + 1) * step;
+        const bool le = at <= hi && seg_first[at] <= j0;          // true on the first c lanes
+        const uint32_t c = (uint32_t)__popcll(__ballot(le));
+        lo += c * step;
+        hi = hi - lo < step - 1u ? hi : lo + step - 1u;
+    }
+    i = lo;
+    jend = j1 < n_out ? j1 : (uint32_t)n_out;
+    return true;
+}
+
+// the scans and the write's grid, the same for both entries: `n` inputs planned into ws
+template <typename... KArgs, typename... Args>
+int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, uint32_t out_cap,
+                   uint32_t* seg_first_dev, uint64_t* totals_dev, hipStream_t st, Args... args) {
+    const uint32_t nb = blocks(n);
+    RPKT_TRY(launch(scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, totals_dev,
+                    seg_first_dev + n));
+    RPKT_TRY(launch(segment_scan_frames_kernel, dim3(nb), dim3(kSegBlock), 0, st, n, ws.part,
+                    seg_first_dev, ws.obase));
+    const uint64_t per_block = (uint64_t)kWavesPerBlock * kSegRun;        // outputs a block
+    const uint32_t wb = (uint32_t)(((uint64_t)out_cap + per_block - 1) / per_block);
+    return launch(write_kernel, dim3(wb), dim3(kSegBlock), 0, st, args...);
+}
 
 // ---- tunnels: the carrier of an inner TCP / UDP frame -----------------------------------
 //

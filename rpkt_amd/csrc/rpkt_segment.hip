@@ -30,7 +30,9 @@
 // What a record says about a TCP or UDP frame (l4_where), the record stage, the block scan and
 // the kernel over the block sums, the copy, the header write, the entries' argument checks and
 // the workspace carving are in rpkt_segcopy.h, which rpkt_coalesce.hip (the inverse entry)
-// shares.
+// shares; the workspace layout (seg_ws), the plan's end (plan_store), the scan over frames, the
+// write's run of outputs (output_run, kSegRun) and scan_and_write are there too, shared with
+// rpkt_fragment.hip (IP fragmentation: the same structure with another header rule).
 // Every load goes through the frames buffer resource and every store through one over
 // [out_frames_dev, + out_bytes); an overflowing batch (totals past the capacities) writes
 // its totals and seg_first and nothing else.
@@ -54,24 +56,6 @@
 #include "rpkt_segcopy.h"
 
 namespace {
-
-// the workspace: per-frame plans (32 B: `quads` 2; the tunnel entry's 64 B: 4), per-frame
-// output byte bases (u64), block sums (count, bytes: u64 pairs)
-struct SegWs {
-    u32x4*    plan;
-    uint64_t* obase;
-    uint64_t* part;
-    size_t    bytes;
-};
-inline SegWs seg_ws(void* ws, uint32_t n, uint32_t quads = 2) {
-    Carve c(ws);
-    SegWs w;
-    w.plan = c.take<u32x4>(quads * (size_t)n);
-    w.obase = c.take<uint64_t>(n);
-    w.part = c.take<uint64_t>(2 * (size_t)blocks(n));
-    w.bytes = c.used();
-    return w;
-}
 
 // plan words: 0 frame offset (chains: the chain's first segment, clamped), 1 frame length
 // (chains: pkt_len), 2 l3 | l4 << 16, 3 payload_off | payload_len << 16, 4 IPv4 constant sum |
@@ -120,23 +104,6 @@ __device__ __forceinline__ void seg_constants(const Header& H, const L4Where& s,
     p[5] = fold16(l4c) | (w12 << 16);
     p[6] = seq;
     p[7] = kSegOn | (s.v6 ? kSegV6 : 0u) | (s.udp ? kSegUdp : 0u);
-}
-
-// The plan's end: frame i's plan (words 0..7 of its kQuads * 16 bytes), count and bytes to the
-// workspace, the block's sums to part.
-template <int kQuads = 2>
-__device__ __forceinline__ void plan_store(bool valid, uint32_t i, const uint32_t (&p)[8],
-                                           uint64_t cnt, uint64_t bytes, u32x4* __restrict__ plan,
-                                           uint32_t* __restrict__ seg_first,
-                                           uint64_t* __restrict__ obase, uint64_t* __restrict__ part,
-                                           uint64_t* red) {
-    if (valid) {
-        plan[kQuads * (size_t)i] = u32x4{p[0], p[1], p[2], p[3]};
-        plan[kQuads * (size_t)i + 1] = u32x4{p[4], p[5], p[6], p[7]};
-        seg_first[i] = (uint32_t)cnt;
-        obase[i] = bytes;
-    }
-    block_sums_to_part(cnt, bytes, part, red);
 }
 
 template <bool kUdp>
@@ -291,23 +258,7 @@ void segment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
     plan_store(valid, i, p, cnt, bytes, plan, seg_first, obase, part, red);
 }
 
-// ---- 2. scan ---------------------------------------------------------------------------
-
-// after scan_parts_kernel (rpkt_segcopy.h) over the block sums, which also stores seg_first[n]:
-// one block per kSegBlock frames: counts and bytes -> seg_first and the output byte bases
-__global__ __launch_bounds__(kSegBlock)
-void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
-                                uint32_t* __restrict__ seg_first, uint64_t* __restrict__ obase) {
-    __shared__ uint64_t red[2 * kWavesPerBlock];
-    const uint32_t i = blockIdx.x * kSegBlock + threadIdx.x;
-    uint64_t a = i < n ? seg_first[i] : 0, b = i < n ? obase[i] : 0;
-    uint64_t ta, tb;
-    block_excl_scan2(a, b, ta, tb, red);
-    if (i < n) {
-        seg_first[i] = (uint32_t)(part[2 * (size_t)blockIdx.x] + a);
-        obase[i] = part[2 * (size_t)blockIdx.x + 1] + b;
-    }
-}
+// ---- 2. scan: scan_parts_kernel and segment_scan_frames_kernel (rpkt_segcopy.h) -------------
 
 // ---- 3. write --------------------------------------------------------------------------
 
@@ -387,52 +338,6 @@ __device__ __forceinline__ void write_output(__amdgpu_buffer_rsrc_t rs, uint32_t
     SegPatch P[kSegPatches];
     seg_patches<kUdp>(o, pb, k, pay, P);
     wave_copy_header(rs, fb, ro, foff, o.d0, o.po, hfirst, P, lane);
-}
-
-// A wave writes kSegRun consecutive outputs.  What precedes an output's first copy load is a
-// chain of dependent loads (the totals, the search, the plan), microseconds against the
-// fraction of one that 1.5 KB take to copy; with one output a wave that chain bounded the
-// kernel at 0.55 of the same bytes' device copy.  Here the search is done once for the run,
-// and the outputs after the first find their frame by stepping along seg_first.
-#ifndef RPKT_SEG_RUN
-#define RPKT_SEG_RUN 8
-#endif
-constexpr uint32_t kSegRun = RPKT_SEG_RUN;
-
-// The wave's run of outputs [j0, jend) and the input frame i of output j0; false when the
-// wave has nothing to write (past out_cap, an overflowing batch, only spare slots, whose
-// offsets it fills).  Wave-uniform throughout.
-__device__ __forceinline__ bool output_run(uint32_t n, const uint32_t* __restrict__ seg_first,
-                                           const uint64_t* __restrict__ totals, uint32_t out_bytes,
-                                           uint32_t* __restrict__ out_offsets, uint32_t out_cap,
-                                           int lane, uint32_t& j0, uint32_t& jend, uint32_t& i) {
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t j64 = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kSegRun;
-    if (j64 >= out_cap) return false;
-    j0 = (uint32_t)j64;
-    const uint32_t j1 = out_cap - j0 < kSegRun ? out_cap : j0 + kSegRun;   // outputs [j0, j1)
-    const uint64_t n_out = totals[0], need = totals[1];
-    if (n_out > out_cap || need > out_bytes) return false;        // overflow: the totals say so
-    // spare slots are empty frames at the end
-    if ((uint32_t)lane < j1 - j0 && j0 + (uint32_t)lane >= n_out)
-        out_offsets[j0 + (uint32_t)lane + 1u] = (uint32_t)need;
-    if (j0 >= n_out) return false;
-    if (j0 == 0u && lane == 0) out_offsets[0] = 0u;
-    // the input frame of output j0: the last i with seg_first[i] <= j0 (every frame has an
-    // output, so i <= j0).  64 probes a round, one per lane: three dependent loads at
-    // n = 32,768 where a binary search has fifteen.
-    uint32_t lo = 0, hi = j0 < n - 1u ? j0 : n - 1u;
-    while (lo < hi) {
-        const uint32_t step = (hi - lo) / kWave + 1u;
-        const uint64_t at = (uint64_t)lo + (uint64_t)(lane + 1) * step;
-        const bool le = at <= hi && seg_first[at] <= j0;          // true on the first c lanes
-        const uint32_t c = (uint32_t)__popcll(__ballot(le));
-        lo += c * step;
-        hi = hi - lo < step - 1u ? hi : lo + step - 1u;
-    }
-    i = lo;
-    jend = j1 < n_out ? j1 : (uint32_t)n_out;
-    return true;
 }
 
 template <bool kUdp>
@@ -909,20 +814,6 @@ void segment_tunnel_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_
         }
         write_tunnel_chain_output<kUdp>(rs, S, n_segs, ro, out_offsets, mss, j, j - cur, t, lane);
     }
-}
-
-// the scans and the write's grid, the same for both entries: `n` inputs planned into ws
-template <typename... KArgs, typename... Args>
-int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, uint32_t out_cap,
-                   uint32_t* seg_first_dev, uint64_t* totals_dev, hipStream_t st, Args... args) {
-    const uint32_t nb = blocks(n);
-    RPKT_TRY(launch(scan_parts_kernel, dim3(1), dim3(kSegBlock), 0, st, ws.part, nb, totals_dev,
-                    seg_first_dev + n));
-    RPKT_TRY(launch(segment_scan_frames_kernel, dim3(nb), dim3(kSegBlock), 0, st, n, ws.part,
-                    seg_first_dev, ws.obase));
-    const uint64_t per_block = (uint64_t)kWavesPerBlock * kSegRun;        // outputs a block
-    const uint32_t wb = (uint32_t)(((uint64_t)out_cap + per_block - 1) / per_block);
-    return launch(write_kernel, dim3(wb), dim3(kSegBlock), 0, st, args...);
 }
 
 }  // namespace

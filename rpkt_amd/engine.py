@@ -92,6 +92,9 @@ ABI = {
     "rpkt_gpu_segment_tunnel_chains_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_segment_tunnel_chains": (_i, [_C, _p, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32,
                                             _p, _p, _p, _p]),
+    "rpkt_gpu_fragment_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_fragment_batch": (_i, [_B, _p, _u32, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
+                                     _p, _p]),
     "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p, _p]),
@@ -757,6 +760,42 @@ def segment_tunnel_chains(chains, outer, tun, inner, mss, out_frames=None, out_o
     return _segment_tunnel("rpkt_gpu_segment_tunnel_chains", chains, "segment_tunnel_chains", outer,
                            tun, inner, mss, out_frames, out_offsets, out_cap, out_bytes, seg_first,
                            totals, workspace, stream, header_max, udp)
+
+
+FRAGMENT_IGNORE_DF = 1
+
+
+def fragment_workspace(n, device="cuda"):
+    """The workspace tensor of fragment_batch for n input frames
+    (rpkt_gpu_fragment_workspace_bytes)."""
+    return _workspace("fragment", n, device)
+
+
+def fragment_batch(batch, recs, mtu, ignore_df=False, ip6_ident=0, out_frames=None,
+                   out_offsets=None, out_cap=None, out_bytes=None, frag_first=None, totals=None,
+                   workspace=None, l3_header_max=60, stream=None):
+    """rpkt_gpu_fragment_batch: IPv4 / IPv6 fragmentation of `batch` at the L3 MTU `mtu`, located
+    by `recs` (parse_batch's records of this batch, with F_IPV6 for IPv6 frames to be cut).
+    ignore_df (RPKT_FRAGMENT_IGNORE_DF) also cuts IPv4 packets that have DF set; ip6_ident + i is
+    the identification in frame i's IPv6 Fragment headers.  Returns (out, frag_first, totals) as
+    segment_batch returns (out, seg_first, totals), under the same overflow rule.
+    By default the outputs are sized from the documented bound: out_cap = n + frames_bytes //
+    max(8, (mtu - l3_header_max - 8) & ~7) slots, l3_header_max the longest per-fragment L3
+    header of the batch (IPv4: ihl; IPv6: 40 and the extension headers up to the last Routing
+    header), and out_bytes = frames_bytes + (out_cap - n) * (22 + l3_header_max + 8) bytes:
+    Ethernet with two tags, that header and a Fragment header before each further slice."""
+    n, fbytes = batch.n, batch.frames.numel()
+    out_frames, out_bytes, out_offsets, out_cap, frag_first, totals, workspace = _reframe_outputs(
+        "fragment_batch", batch, recs,
+        lambda: n + fbytes // max(8, (mtu - l3_header_max - 8) & ~7),
+        lambda cap: fbytes + (cap - n) * (22 + l3_header_max + 8),
+        out_frames, out_offsets, out_cap, out_bytes, frag_first, "frag_first", totals, workspace,
+        "fragment")
+    _call("rpkt_gpu_fragment_batch", ctypes.byref(batch.desc()), recs.data_ptr(), mtu,
+          FRAGMENT_IGNORE_DF if ignore_df else 0, ip6_ident & 0xffffffff, out_frames.data_ptr(),
+          out_bytes, out_offsets.data_ptr(), out_cap, frag_first.data_ptr(), totals.data_ptr(),
+          workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), frag_first, totals
 
 
 COALESCE_TRUST_SUMS = 1

@@ -29,7 +29,9 @@ wrapped in a second tunnel by k % 6) through the tunnel parse and two next-level
 (rpkt_gpu_parse_tunnel_next, records and flow events) against the oracle composition; (e) a
 fuzzed tunnel chain batch (config 13 / 14) through rpkt_gpu_segment_tunnel_chains at a random mss
 and flag, with the chain tunnel parse's records or the flat ones of the flattened bytes, against
-tests/segment_tunnel_chains_model.py.  Build and forward rewrite frames in place, so they run on generator batches
+tests/segment_tunnel_chains_model.py; (f) a generator batch (options, fuzz, dual-stack, dual-stack
+fuzz or tunnel configs) through rpkt_gpu_fragment_batch at a random mtu, with or without
+RPKT_FRAGMENT_IGNORE_DF and with a random ip6_ident, against tests/fragment_model.py.  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -49,6 +51,7 @@ from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_recor
                               as_records16, as_tunnels, project16)
 
 import coalesce_tunnel_model  # noqa: E402
+import fragment_model  # noqa: E402
 import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
 import segment_chains_model  # noqa: E402
@@ -397,6 +400,24 @@ def check_segment_tunnel_chains(rng, seed):
             "n_out": int(totals[0]), "cut": [kinds[k] for k in (0, 1, 2, 3)]}
 
 
+def check_fragment(rng, seed):
+    """rpkt_gpu_fragment_batch on a generator batch at a random mtu, with or without
+    RPKT_FRAGMENT_IGNORE_DF, against tests/fragment_model.py."""
+    cfg = int(rng.choice([4, 5, 6, 11, 12, 13, 14]))
+    hb = gen.make_batch(cfg, int(rng.integers(1, 3000)), seed=seed)
+    mtu = int(rng.choice([28, 29, 36, 48, 68, 100, 300, 576, 1280, 1500, 65535]))
+    ignore_df, ident = bool(rng.random() < 0.7), int(rng.integers(0, 1 << 32))
+    out, first, totals = fragment_model.fragment(hb, segment_model.oracle_records(hb), mtu, ignore_df,
+                                                 ident)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    db = engine.DeviceBatch.from_host(hb)
+    odb, gf, gt = engine.fragment_batch(db, engine.parse_batch(db, segment_model.F6), mtu, ignore_df,
+                                        ident, out_cap=out_cap,
+                                        out_bytes=int(totals[1]) + int(rng.integers(0, 40)))
+    same_reframed("fragment_batch", odb, gf, gt, out, first, totals, out_cap)
+    return {"cfg": cfg, "n": int(hb.n), "mtu": mtu, "ignore_df": ignore_df, "n_out": int(totals[0])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=8.0)
@@ -435,6 +456,8 @@ def main():
                 rec["tunnel_next"] = check_tunnel_next(rng, seed)
                 step = "segment_tunnel_chains"
                 rec["segment_tunnel_chains"] = check_segment_tunnel_chains(rng, seed)
+                step = "fragment"
+                rec["fragment"] = check_fragment(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")
