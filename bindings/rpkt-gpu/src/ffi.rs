@@ -79,6 +79,8 @@ pub const RPKT_COALESCE_UDP: u32 = 16;
 pub const RPKT_SEGMENT_UDP: u32 = 16;
 /// rpkt_gpu_fragment_batch: cut IPv4 packets that have DF set, too
 pub const RPKT_FRAGMENT_IGNORE_DF: u32 = 1;
+/// rpkt_gpu_reassemble_batch / _keys: do not require a valid IPv4 header sum
+pub const RPKT_REASSEMBLE_TRUST_SUMS: u32 = 1;
 
 // enum rpkt_opt_stop / rpkt_layer_stop
 pub const RPKT_OPT_NONE: u8 = 0;
@@ -441,6 +443,22 @@ extern "C" {
                                    out_offsets_dev: *mut u32, out_cap: u32,
                                    frag_first_dev: *mut u32, totals_dev: *mut u64,
                                    workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_reassemble_batch for n positions.
+    pub fn rpkt_gpu_reassemble_workspace_bytes(n: u32) -> usize;
+    /// IPv4 / IPv6 reassembly on the device: consecutive positions, taken in `order_dev`'s order
+    /// (NULL: frame order), that hold consecutive fragments of one datagram are merged into one
+    /// frame (a complete IPv6 datagram loses its Fragment header), every other frame copied; the
+    /// output is a packed batch of `out_cap` slots.
+    pub fn rpkt_gpu_reassemble_batch(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
+                                     order_dev: *const u32, flags: u32,
+                                     out_frames_dev: *mut u8, out_bytes: u64,
+                                     out_offsets_dev: *mut u32, out_cap: u32,
+                                     src_first_dev: *mut u32, totals_dev: *mut u64,
+                                     workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// The sort keys for rpkt_gpu_reassemble_batch: a stable ascending sort of `keys_dev` (n
+    /// u64) is an `order_dev` with every datagram's fragments adjacent, ascending in offset.
+    pub fn rpkt_gpu_reassemble_keys(batch: *const rpkt_batch_t, recs_dev: *const rpkt_rec_t,
+                                    flags: u32, keys_dev: *mut u64, stream: *mut c_void) -> c_int;
     /// Workspace of rpkt_gpu_coalesce_batch for n positions.
     pub fn rpkt_gpu_coalesce_workspace_bytes(n: u32) -> usize;
     /// TCP receive coalescing (GRO / LRO) on the device: consecutive in-order TCP segments of

@@ -569,6 +569,39 @@ pub unsafe fn fragment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mt
                                        out.seg_first_dev, out.totals_dev, workspace_dev, stream))
 }
 
+/// rpkt_gpu_reassemble_workspace_bytes: the workspace of reassemble_batch for `n` positions.
+pub fn reassemble_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_reassemble_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_reassemble_batch: IPv4 / IPv6 reassembly of a parsed batch, its positions taken in
+/// `order_dev`'s order (null: frame order).  `flags`: 0 or `ffi::RPKT_REASSEMBLE_TRUST_SUMS`.
+/// `out` is laid out as coalesce_batch's; `out_mss_dev` is not used.
+///
+/// # Safety
+/// As for `coalesce_batch`, with `workspace_dev` holding `reassemble_workspace_bytes(batch.n)`
+/// bytes (16-byte aligned).
+pub unsafe fn reassemble_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec,
+                               order_dev: *const u32, flags: u32, out: &CoalesceOut,
+                               workspace_dev: *mut core::ffi::c_void,
+                               stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_reassemble_batch(batch, recs_dev, order_dev, flags, out.frames_dev,
+                                         out.out_bytes, out.offsets_dev, out.out_cap,
+                                         out.src_first_dev, out.totals_dev, workspace_dev, stream))
+}
+
+/// rpkt_gpu_reassemble_keys: the sort keys of a parsed batch for reassemble_batch (`keys_dev`:
+/// `batch.n` u64, 8-byte aligned).  A stable ascending sort of them is an `order_dev`.
+///
+/// # Safety
+/// `batch` must describe device memory valid for the call; `recs_dev` must be the records a
+/// parse wrote for this same batch; `keys_dev` must be device memory of `batch.n` u64.
+pub unsafe fn reassemble_keys(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, flags: u32,
+                              keys_dev: *mut u64,
+                              stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_reassemble_keys(batch, recs_dev, flags, keys_dev, stream))
+}
+
 /// The outputs of rpkt_gpu_coalesce_batch: a packed batch of `out_cap` slots (`frames_dev`,
 /// `out_bytes` bytes, 16-byte aligned; `offsets_dev`, `out_cap + 1` entries), the first
 /// position of every output (`src_first_dev`, `n + 1` entries), each merged output's segment

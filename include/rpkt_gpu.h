@@ -124,7 +124,13 @@ enum rpkt_status {
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
  *     mss's place;
  *   rpkt_gpu_coalesce_tunnel_batch: rpkt_gpu_coalesce_batch's order with outer_dev, tun_dev and
- *     inner_dev in recs_dev's places: each required (E_INVAL) and 16-byte aligned (E_ALIGN).
+ *     inner_dev in recs_dev's places: each required (E_INVAL) and 16-byte aligned (E_ALIGN);
+ *   rpkt_gpu_reassemble_batch: rpkt_gpu_coalesce_batch's order without a max_payload (order_dev
+ *     may be NULL), flags other than 0 or RPKT_REASSEMBLE_TRUST_SUMS;
+ *   rpkt_gpu_reassemble_keys: the batch entries' order: a NULL batch, recs_dev or keys_dev
+ *     (E_INVAL); flags other than 0 or RPKT_REASSEMBLE_TRUST_SUMS (E_INVAL); n == 0 (RPKT_OK);
+ *     NULL frames_dev (E_INVAL); frames_bytes (E_TOO_LARGE); no layout (E_INVAL); alignment
+ *     (E_ALIGN): recs_dev 16 B, keys_dev 8 B.
  * Where an entry leaves that order (kept as it is, callers may rely on it):
  *   rpkt_gpu_parse_tunnel_batch and each slot of rpkt_gpu_parse_tunnel_ring test the flow
  *     events first, before n == 0: an empty batch with RPKT_F_FLOW_EV and no event buffer is
@@ -1046,9 +1052,8 @@ int rpkt_gpu_segment_tunnel_chains(const rpkt_chains_t* chains, const rpkt_rec_t
  * A tunnelled frame is to this entry what its outer record says: the OUTER IP packet is
  * fragmented, which is what a VTEP does with an encapsulation that is over the MTU.
  * Argument checks: rpkt_gpu_segment_batch's in its order (at enum rpkt_err).
- * Not covered: reassembly (the receive-side inverse: a match across frames on source,
- * destination, protocol and identification); fragmentation over mbuf chains; fragmenting the
- * inner packet of a tunnel; an MTU per frame. */
+ * Not covered: fragmentation over mbuf chains; fragmenting the inner packet of a tunnel; an MTU
+ * per frame.  The receive-side inverse is rpkt_gpu_reassemble_batch, below. */
 #define RPKT_FRAGMENT_IGNORE_DF 1u   /* cut IPv4 packets that have DF set, too */
 
 size_t rpkt_gpu_fragment_workspace_bytes(uint32_t n);
@@ -1058,6 +1063,129 @@ int rpkt_gpu_fragment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_de
                             uint32_t* out_offsets_dev, uint32_t out_cap,
                             uint32_t* frag_first_dev, uint64_t* totals_dev,
                             void* workspace_dev, void* stream);
+
+/* ---- IPv4 / IPv6 reassembly --------------------------------------------------------- */
+
+/* The receive-side inverse of rpkt_gpu_fragment_batch.  Without it a fragmented datagram is lost
+ * to the receive path: the parser reports an IPv6 fragment as RPKT_S_IP6_FRAGMENT with no upper
+ * layer, parses a non-first IPv4 fragment as if its payload were an L4 header, and a VTEP whose
+ * peer fragmented an over-MTU encapsulation cannot get at the inner frame.
+ * rpkt_gpu_reassemble_batch merges consecutive positions that hold consecutive fragments of one
+ * datagram into one frame on the device.  The output is the complete batch in position order:
+ * every position ends up in exactly one output frame.  The rule is per position and local: no
+ * table, no timers, one batch.  rpkt_gpu_reassemble_keys, below, gives the order that brings a
+ * datagram's fragments to consecutive positions.
+ *
+ * recs_dev: the rpkt_rec_t records of a parse of this same batch (RPKT_F_IPV6 for IPv6 fragments;
+ * RPKT_F_IP_SUM unless RPKT_REASSEMBLE_TRUST_SUMS).  They only locate things and give the
+ * verdict -- status, the dispatch ethertype, l3_off, l4_off, ip_sum -- and every header byte is
+ * read from the frame.  order_dev (optional, n entries): position i holds frame order[i] (NULL:
+ * frame i).  An entry >= n makes its position an empty frame: never read, a zero-length output.
+ * It need not be a permutation.  flags: 0 or RPKT_REASSEMBLE_TRUST_SUMS.  Below l3 = l3_off,
+ * l4 = l4_off.
+ *
+ * A position is an eligible IPv4 FRAGMENT iff all of these hold, with ihl (the low nibble of
+ * byte l3, times 4), L (be16 at l3 + 2) and the frag word fw (be16 at l3 + 6) from the frame:
+ *   - the dispatch ethertype is 0x0800 and status is one under which the IPv4 header parsed:
+ *     OK, L4_OTHER, UDP_SHORT, UDP_BAD_LEN, TCP_SHORT, TCP_BAD_DOFF, ICMP_EMPTY;
+ *   - ihl in 20..60 and l4 == l3 + ihl;
+ *   - l3 + L <= frame_len and P = L - ihl >= 1;
+ *   - (fw & 0x3fff) != 0: MF set, or an offset;
+ *   - with off = (fw & 0x1fff) * 8, ihl + off + P <= 65535, so no merge overflows packet_len;
+ *   - without TRUST_SUMS, ip_sum == 0xffff.
+ * A position is an eligible IPv6 FRAGMENT iff all of these hold, with x the start of its
+ * Fragment header:
+ *   - the dispatch ethertype is 0x86DD and status is RPKT_S_IP6_FRAGMENT;
+ *   - x = l4 - 8 >= l3 + 40;
+ *   - a walk in the frame from l3 + 40 with the fixed header's next_header, at most
+ *     RPKT_MAX_IP6_EXT headers, meets only types 0, 43 and 60 (each 8 * (1 + byte 1) long) and 51
+ *     (4 * (2 + byte 1) long) and arrives exactly at x with type 44;
+ *   - with E = l3 + 40 + payload_len (be16 at l3 + 4), E <= frame_len and P = E - (x + 8) >= 1;
+ *   - with off = be16 at x + 2 masked with 0xfff8 and M its bit 0, (x - l3 - 40) + 8 + off + P
+ *     <= 65535, so no merge overflows payload_len.
+ * An atomic fragment (offset 0, M clear) is parsed on by rpkt_gpu_parse_batch and is never
+ * eligible.
+ *
+ * B(i), "position i continues position i - 1" (B(0) false), holds iff both are eligible and of
+ * the same IP version with equal l3 and l4; position i - 1 has MF / M set and P_{i-1} % 8 == 0;
+ * off_i == off_{i-1} + P_{i-1}; and
+ *   IPv4: bytes [0, l3) are equal, and ident, protocol, source and destination.  TOS, TTL, the
+ *         options, DF and the reserved bit are the head's and are not compared;
+ *   IPv6: bytes [0, x + 8) are equal, ignoring l3+4..5 (payload_len) and x+2..3 (offset, M): so
+ *         every extension header before the Fragment header, its next_header and the
+ *         identification match.
+ * A run of links is one group: there is no greedy cut, the 65535 conditions above already bound
+ * every merge.  Overlapping, duplicated and out-of-order fragments do not link and pass through.
+ *
+ * Outputs, in position order, one per group:
+ *   a group of one position   a byte copy of [0, frame_len), padding included;
+ *   a merged IPv4 group       the head's bytes [0, l4), then every member's [l4, l4 + P) in order
+ *                             (Ethernet padding is not carried); packet_len = ihl + the total;
+ *                             the frag word the head's with MF replaced by the last member's; the
+ *                             header checksum filled as RPKT_BUILD_IP_CSUM fills it;
+ *   a merged IPv6 group that is not complete
+ *                             the head's bytes [0, x + 8), then every member's [x + 8, + P);
+ *                             payload_len = (x - l3 - 40) + 8 + the total; bytes 2..3 of the
+ *                             Fragment header = the head's offset | the last member's M;
+ *   a merged IPv6 group that is complete (the head's offset 0, the last member's M clear)
+ *                             the Fragment header is removed: the head's bytes [0, x) with the
+ *                             next-header byte of the last header before x (byte l3 + 6 when
+ *                             there is none) set to the Fragment header's byte 0, then the
+ *                             payloads; payload_len = (x - l3 - 40) + the total.
+ * A complete IPv4 group needs no other treatment: its frag word comes out 0 but for the head's DF
+ * and reserved bit.  A partial merge is a valid, larger fragment, so the entry composes: a second
+ * call, or a later batch that carries the partial outputs along, finishes the merge; this is the
+ * inverse of "a fragment is cut again like any other".
+ * The inverse property: reassemble(fragment(F)) == F byte for byte, whatever the mtu and also for
+ * frames that were fragments already, for every frame F whose IP packet ends at the frame's end
+ * and whose IPv4 frag word has DF and the reserved bit clear; for the others it is F without its
+ * padding and without those two bits, which rpkt_gpu_fragment_batch drops.
+ *
+ * src_first_dev (n + 1 entries: output j is made of positions [src_first[j], src_first[j+1]);
+ * entries n_out+1..n equal n), totals_dev, out_frames_dev, out_bytes, out_offsets_dev and out_cap
+ * are rpkt_gpu_coalesce_batch's word for word: totals {n_out, out_bytes_needed} and src_first
+ * exact on overflow with the rest unspecified, spare offset slots equal out_bytes_needed, nothing
+ * ever written outside [out_frames_dev, + out_bytes) and out_offsets_dev[0..out_cap].
+ * Bounds for sizing: n_out <= n; out_bytes_needed <= the sum of the positions' frame lengths.
+ * workspace_dev: rpkt_gpu_reassemble_workspace_bytes(n) bytes, 16-byte aligned; calls that share
+ * one must be ordered.  The call is plan, prefix sums and write on `stream` with no host step:
+ * parse -> keys -> (the caller's sort) -> reassemble -> parse captures as one graph.  Records from
+ * another batch give wrong frames but never a fault: every load of frame bytes goes through the
+ * frames buffer resource, every store through the one over the output, and offsets that do not
+ * nest make a position ineligible.
+ * Argument checks: rpkt_gpu_coalesce_batch's in its order, without a max_payload (at enum
+ * rpkt_err).
+ * Not covered: state across batches (timers, a fragment table: a caller carries partial outputs
+ * into the next batch); overlap resolution; mbuf chains; the inner packet of a tunnel (to this
+ * entry a tunnelled frame is what its outer record says: the OUTER fragments are merged, and
+ * rpkt_gpu_parse_tunnel_batch of the output reaches the inner frame); an output cap below
+ * 65,535. */
+#define RPKT_REASSEMBLE_TRUST_SUMS 1u   /* do not require a valid IPv4 header sum */
+
+size_t rpkt_gpu_reassemble_workspace_bytes(uint32_t n);
+int rpkt_gpu_reassemble_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev,
+                              const uint32_t* order_dev,      /* optional, n entries */
+                              uint32_t flags,
+                              uint8_t* out_frames_dev, uint64_t out_bytes,
+                              uint32_t* out_offsets_dev, uint32_t out_cap,
+                              uint32_t* src_first_dev,        /* n + 1 entries */
+                              uint64_t* totals_dev, void* workspace_dev, void* stream);
+
+/* The sort keys that order a batch for rpkt_gpu_reassemble_batch.  Flow events key on the
+ * 5-tuple of an L4 header that fragments after the first do not have, so they cannot order
+ * fragments.  keys_dev[i] (n entries, 8-byte aligned), with the eligibility above (same flags):
+ *   an eligible fragment   (h & 0x7fffffff) << 32 | off / 8, h = rpkt_flow_hash(src, dst,
+ *                          ident & 0xffff, ident >> 16, proto): IPv4 the record's ip_src / ip_dst,
+ *                          the 16-bit ident and the protocol from the frame; IPv6 the record's
+ *                          ip6_src_fold / ip6_dst_fold, the 32-bit identification and 44;
+ *   every other frame      1 << 63 | i.
+ * A stable ascending sort of the keys as unsigned 64-bit numbers (the caller's: any device or
+ * host sort) is an order_dev: each datagram's fragments adjacent and ascending in offset
+ * whatever their arrival order, every non-fragment after them in arrival order.  A hash collision
+ * only interleaves two datagrams, which then merge less: the link compares the real bytes.
+ * One launch on `stream`. */
+int rpkt_gpu_reassemble_keys(const rpkt_batch_t* batch, const rpkt_rec_t* recs_dev,
+                             uint32_t flags, uint64_t* keys_dev /* n, 8-B aligned */, void* stream);
 
 /* ---- TCP and UDP receive coalescing (GRO / LRO, UDP GRO) --------------------------- */
 

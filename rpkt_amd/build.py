@@ -26,7 +26,7 @@ GEN_LIB = os.path.join(OUT, "librpkt_gen.so")
 GPU_SRC = [os.path.join(HERE, "csrc", f) for f in
            ("rpkt_parse.hip", "rpkt_tx.hip", "rpkt_walks.hip", "rpkt_fields.hip", "rpkt_tunnel.hip",
             "rpkt_tunnel_chains.hip", "rpkt_tunnel_next.hip", "rpkt_segment.hip", "rpkt_coalesce.hip",
-            "rpkt_fragment.hip", "rpkt_abi.hip", "rpkt_coll.hip")]
+            "rpkt_fragment.hip", "rpkt_reassemble.hip", "rpkt_abi.hip", "rpkt_coll.hip")]
 GPU_DEPS = [os.path.join(HERE, "csrc", h) for h in
             ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h", "rpkt_chain.h", "rpkt_tunnel.h",
              "rpkt_segcopy.h", "rpkt_proto_table.h")]                 # included; the table is generated
@@ -52,6 +52,7 @@ UNIT_HEADERS = {"rpkt_parse.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h"
                 "rpkt_segment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
                 "rpkt_coalesce.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
                 "rpkt_fragment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
+                "rpkt_reassemble.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
                 "rpkt_abi.hip": ("rpkt_common.h",),
                 "rpkt_coll.hip": ("rpkt_common.h",)}
 # every unit has its header list (a unit added to GPU_SRC without one would make
@@ -91,7 +92,7 @@ def unit_hashes(defines=()):
     kernel family stays valid while another unit changes: "parse=... tx=... walks=..."."""
     return " ".join("%s=%s" % (u, source_hash(["rpkt_%s.hip" % u], defines))
                     for u in ("parse", "tx", "walks", "fields", "tunnel", "tunnel_chains", "tunnel_next",
-                              "segment", "coalesce", "fragment"))
+                              "segment", "coalesce", "fragment", "reassemble"))
 
 
 def build_gpu(force=False, extra=()):
@@ -135,7 +136,7 @@ def build_gen(force=False):
 
 
 EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "tso_tx_chains", "lro_rx",
-            "vtep_tx", "vtep_gro_rx", "vtep_tx_chains", "vtep_frag_tx")
+            "vtep_tx", "vtep_gro_rx", "vtep_tx_chains", "vtep_frag_tx", "vtep_frag_rx")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "parse_batch")
 FLOW_REDUCE_BIN = os.path.join(ROOT, "examples", "flow_reduce")
 VTEP_RX_BIN = os.path.join(ROOT, "examples", "vtep_rx")
@@ -146,6 +147,7 @@ VTEP_TX_BIN = os.path.join(ROOT, "examples", "vtep_tx")
 VTEP_GRO_RX_BIN = os.path.join(ROOT, "examples", "vtep_gro_rx")
 VTEP_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "vtep_tx_chains")
 VTEP_FRAG_TX_BIN = os.path.join(ROOT, "examples", "vtep_frag_tx")
+VTEP_FRAG_RX_BIN = os.path.join(ROOT, "examples", "vtep_frag_rx")
 
 
 def build_example(force=False):

@@ -32,8 +32,9 @@
 // its price is the second pass over the merged outputs' headers.  No kernel waits on
 // another workgroup and every loop is bounded by a count from the plan.
 // Shared with rpkt_segment.hip through rpkt_segcopy.h: which records are the TCP frames that
-// segmentation cuts (l4_where), the record stage, the block scan and launch 5, the copy, the
-// header write, the entry's argument checks and the workspace carving.
+// segmentation cuts (l4_where), the record stage, the block scans and launches 3 and 5, the walk
+// of a header's dwords, the copy, the header write, the entry's argument checks and the
+// workspace carving (rpkt_reassemble.hip follows the same launches with a fragment rule).
 // Every load of frame bytes goes through the frames buffer resource and every store of
 // output bytes through one over [out_frames_dev, + out_bytes); an overflowing call (totals
 // past the capacities) writes its totals, src_first and out_mss and nothing else.
@@ -327,20 +328,6 @@ __device__ __forceinline__ uint32_t outer_keep(uint32_t x, u32x4 t) {
     return m;
 }
 
-// the frame-relative dwords of a header in turn: one aligned load a step
-struct HeaderWalk {
-    uint32_t a4, sh, lo;
-    __device__ __forceinline__ HeaderWalk(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t s)
-        : a4(s & ~3u), sh(s & 3u), lo(ldw(rs, fb, s & ~3u)) {}
-    __device__ __forceinline__ uint32_t next(__amdgpu_buffer_rsrc_t rs, uint32_t fb) {
-        const uint32_t hi = ldw(rs, fb, a4 + 4u);
-        const uint32_t v = align_bytes(hi, lo, sh);
-        lo = hi;
-        a4 += 4u;
-        return v;
-    }
-};
-
 // B(i), i >= 1: the frame at position i continues the one at i - 1
 template <bool kUdp, bool kTun>
 __device__ __forceinline__ bool base_pred(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
@@ -383,19 +370,6 @@ __device__ __forceinline__ bool base_pred(__amdgpu_buffer_rsrc_t rs, uint32_t fb
     return true;
 }
 
-// inclusive max-scan over the block's kSegBlock threads; red: kWavesPerBlock u32 of LDS
-__device__ __forceinline__ uint32_t block_incl_max(uint32_t v, uint32_t* red) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    uint32_t x = wave_incl_max(v);
-    if (lane == kWave - 1) red[wave] = x;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w)
-        if (w < wave) x = max(x, red[w]);
-    __syncthreads();                                              // red is free for the next call
-    return x;
-}
-
 // tplan: the tunnel entry's (<kTun>), else unused
 template <bool kUdp, bool kTun>
 __global__ __launch_bounds__(kSegBlock)
@@ -427,22 +401,7 @@ void coalesce_link_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint3
 
 // ---- 3. heads --------------------------------------------------------------------------
 
-// one block: pmax[b] becomes the index + 1 of the last run head in blocks 0..b
-__global__ __launch_bounds__(kSegBlock)
-void coalesce_scan_heads_kernel(uint32_t* __restrict__ pmax, uint32_t nb) {
-    __shared__ uint32_t red[kWavesPerBlock];
-    __shared__ uint32_t last;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kSegBlock) {
-        const uint32_t k = base + threadIdx.x;
-        const uint32_t x = max(block_incl_max(k < nb ? pmax[k] : 0u, red), carry);
-        if (k < nb) pmax[k] = x;
-        if (threadIdx.x == kSegBlock - 1) last = x;
-        __syncthreads();
-        carry = last;
-        __syncthreads();
-    }
-}
+// the blocks' run heads' scan: scan_heads_kernel (rpkt_segcopy.h)
 
 // ---- 4. group --------------------------------------------------------------------------
 
@@ -723,7 +682,7 @@ int link_and_write(const rpkt_batch_t* b, const CoWs& ws, uint32_t max_payload,
     const u32x4* tplan = ws.tplan;
     RPKT_TRY(launch(coalesce_link_kernel<kUdp, kTun>, per, blk, 0, st, b->frames_dev, fb, n, ws.plan,
                     ws.aux, ws.pmax, tplan));
-    RPKT_TRY(launch(coalesce_scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
+    RPKT_TRY(launch(scan_heads_kernel, dim3(1), blk, 0, st, ws.pmax, nb));
     RPKT_TRY(launch(coalesce_group_kernel<kTun>, per, blk, 0, st, n, max_payload, ws.plan, ws.aux,
                     ws.pmax, ws.obase, ws.part, tplan));
     RPKT_TRY(launch(scan_parts_kernel, dim3(1), blk, 0, st, ws.part, nb, totals_dev,

@@ -1,11 +1,12 @@
 // rpkt_segcopy.h — what the units that re-frame a batch share (rpkt_segment.hip and
-// rpkt_fragment.hip: one frame into many; rpkt_coalesce.hip: many into one).  Host: the
-// entries' argument checks, the carving of their workspaces and, for the two that cut, the
-// launch of the scans and the write.  Device: what a record says about a TCP or UDP frame, a
+// rpkt_fragment.hip: one frame into many; rpkt_coalesce.hip and rpkt_reassemble.hip: many into
+// one).  Host: the entries' argument checks, the carving of their workspaces and, for the two
+// that cut, the launch of the scans and the write.  Device: what a record says about a TCP or UDP frame, a
 // tile's records staged through LDS, header sums by one lane, the block scans of the plan ->
 // scan -> write structure, the end of a plan kernel and the start of a write kernel's wave
-// (its run of outputs and their input frame), and the wave copy between any two byte phases
-// that sums what it copies.
+// (its run of outputs and their input frame), for runs of positions the block max-scan, the
+// scan of the blocks' run heads and the walk of a header's dwords, and the wave copy between
+// any two byte phases that sums what it copies.
 // Everything is inline in an anonymous namespace.
 #pragma once
 #include "rpkt_common.h"
@@ -287,6 +288,53 @@ void segment_scan_frames_kernel(uint32_t n, const uint64_t* __restrict__ part,
         obase[i] = part[2 * (size_t)blockIdx.x + 1] + b;
     }
 }
+
+// ---- runs of positions (rpkt_coalesce.hip, rpkt_reassemble.hip) ---------------------------
+
+// inclusive max-scan over the block's kSegBlock threads; red: kWavesPerBlock u32 of LDS
+__device__ __forceinline__ uint32_t block_incl_max(uint32_t v, uint32_t* red) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    uint32_t x = wave_incl_max(v);
+    if (lane == kWave - 1) red[wave] = x;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w)
+        if (w < wave) x = max(x, red[w]);
+    __syncthreads();                                              // red is free for the next call
+    return x;
+}
+
+// one block: pmax[b] becomes the index + 1 of the last run head in blocks 0..b
+__attribute__((unused))          // the units that cut have no runs of positions
+__global__ __launch_bounds__(kSegBlock)
+void scan_heads_kernel(uint32_t* __restrict__ pmax, uint32_t nb) {
+    __shared__ uint32_t red[kWavesPerBlock];
+    __shared__ uint32_t last;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nb; base += kSegBlock) {
+        const uint32_t k = base + threadIdx.x;
+        const uint32_t x = max(block_incl_max(k < nb ? pmax[k] : 0u, red), carry);
+        if (k < nb) pmax[k] = x;
+        if (threadIdx.x == kSegBlock - 1) last = x;
+        __syncthreads();
+        carry = last;
+        __syncthreads();
+    }
+}
+
+// the frame-relative dwords of a header in turn: one aligned load a step
+struct HeaderWalk {
+    uint32_t a4, sh, lo;
+    __device__ __forceinline__ HeaderWalk(__amdgpu_buffer_rsrc_t rs, uint32_t fb, uint32_t s)
+        : a4(s & ~3u), sh(s & 3u), lo(ldw(rs, fb, s & ~3u)) {}
+    __device__ __forceinline__ uint32_t next(__amdgpu_buffer_rsrc_t rs, uint32_t fb) {
+        const uint32_t hi = ldw(rs, fb, a4 + 4u);
+        const uint32_t v = align_bytes(hi, lo, sh);
+        lo = hi;
+        a4 += 4u;
+        return v;
+    }
+};
 
 // bytes [lo, hi) of dword v to the output at x (4-B aligned): one dword store, or bytes
 __device__ __forceinline__ void store_dword_part(__amdgpu_buffer_rsrc_t ro, uint32_t x, uint32_t v,

@@ -95,6 +95,10 @@ ABI = {
     "rpkt_gpu_fragment_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_fragment_batch": (_i, [_B, _p, _u32, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p]),
+    "rpkt_gpu_reassemble_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_reassemble_batch": (_i, [_B, _p, _p, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
+                                       _p]),
+    "rpkt_gpu_reassemble_keys": (_i, [_B, _p, _u32, _p, _p]),
     "rpkt_gpu_coalesce_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_coalesce_batch": (_i, [_B, _p, _p, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p, _p]),
@@ -796,6 +800,66 @@ def fragment_batch(batch, recs, mtu, ignore_df=False, ip6_ident=0, out_frames=No
           out_bytes, out_offsets.data_ptr(), out_cap, frag_first.data_ptr(), totals.data_ptr(),
           workspace.data_ptr(), _stream_ptr(stream))
     return DeviceBatch(out_frames, out_cap, out_offsets), frag_first, totals
+
+
+REASSEMBLE_TRUST_SUMS = 1
+
+
+def reassemble_workspace(n, device="cuda"):
+    """The workspace tensor of reassemble_batch for n positions
+    (rpkt_gpu_reassemble_workspace_bytes)."""
+    return _workspace("reassemble", n, device)
+
+
+def reassemble_batch(batch, recs, order=None, trust_sums=False, out_frames=None, out_offsets=None,
+                     out_cap=None, out_bytes=None, src_first=None, totals=None, workspace=None,
+                     stream=None):
+    """rpkt_gpu_reassemble_batch: IPv4 / IPv6 reassembly of the fragments of `batch`, located by
+    `recs` (parse_batch's records of this batch, with F_IPV6 for IPv6 fragments and the IP sum
+    unless trust_sums), the positions taken in `order` (an int32 tensor of n frame indices, e.g.
+    reassemble_order's; None: frame order).  Consecutive positions that hold consecutive
+    fragments of one datagram become one frame; every other frame is copied.  Returns (out,
+    src_first, totals) as coalesce_batch does, under the same overflow rule and with the same
+    default sizes: out_cap = n slots and out_bytes = frames_bytes (give out_bytes when an order
+    repeats frames)."""
+    n = batch.n
+    out_frames, out_bytes, out_offsets, out_cap, src_first, totals, workspace = _reframe_outputs(
+        "reassemble_batch", batch, recs, lambda: max(n, 1), lambda cap: batch.frames.numel(),
+        out_frames, out_offsets, out_cap, out_bytes, src_first, "src_first", totals, workspace,
+        "reassemble")
+    if order is not None and (order.numel() < n or order.element_size() != 4):
+        raise RpktError("reassemble_batch: order takes %d 32-bit entries" % n)
+    _call("rpkt_gpu_reassemble_batch", ctypes.byref(batch.desc()), recs.data_ptr(), _ptr(order),
+          REASSEMBLE_TRUST_SUMS if trust_sums else 0, out_frames.data_ptr(), out_bytes,
+          out_offsets.data_ptr(), out_cap, src_first.data_ptr(), totals.data_ptr(),
+          workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), src_first, totals
+
+
+def reassemble_keys(batch, recs, trust_sums=False, keys=None, stream=None):
+    """rpkt_gpu_reassemble_keys: the sort keys of `batch` for reassemble_batch, an int64 tensor of
+    n holding the u64 bits: hash(source, destination, identification, protocol) and the fragment
+    offset for an eligible fragment, 1 << 63 | i for every other frame."""
+    torch = _torch()
+    n = batch.n
+    if recs.numel() != n * REC_BYTES:
+        raise RpktError("reassemble_keys: records do not fit %d frames" % n)
+    if keys is None:
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=batch.frames.device)
+    if keys.numel() < n or keys.element_size() != 8:
+        raise RpktError("reassemble_keys: keys takes %d 64-bit entries" % n)
+    _call("rpkt_gpu_reassemble_keys", ctypes.byref(batch.desc()), recs.data_ptr(),
+          REASSEMBLE_TRUST_SUMS if trust_sums else 0, keys.data_ptr(), _stream_ptr(stream))
+    return keys[:n]
+
+
+def reassemble_order(keys):
+    """The order that brings each datagram's fragments together, ascending in offset, for
+    reassemble_batch: the stable argsort of reassemble_keys' keys as UNSIGNED numbers (bit 63 of
+    the int64 view is flipped first), the u32 indices in an int32 tensor on keys' device (CPU or
+    GPU).  Frames that are no fragments come last, in arrival order."""
+    import torch
+    return torch.sort(keys ^ (-1 << 63), stable=True)[1].to(torch.int32)
 
 
 COALESCE_TRUST_SUMS = 1

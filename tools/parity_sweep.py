@@ -31,7 +31,10 @@ fuzzed tunnel chain batch (config 13 / 14) through rpkt_gpu_segment_tunnel_chain
 and flag, with the chain tunnel parse's records or the flat ones of the flattened bytes, against
 tests/segment_tunnel_chains_model.py; (f) a generator batch (options, fuzz, dual-stack, dual-stack
 fuzz or tunnel configs) through rpkt_gpu_fragment_batch at a random mtu, with or without
-RPKT_FRAGMENT_IGNORE_DF and with a random ip6_ident, against tests/fragment_model.py.  Build and forward rewrite frames in place, so they run on generator batches
+RPKT_FRAGMENT_IGNORE_DF and with a random ip6_ident, against tests/fragment_model.py; (g) the
+model's fragments of such a batch at a random mtu, shuffled, through rpkt_gpu_reassemble_keys and
+rpkt_gpu_reassemble_batch (under engine.reassemble_order of the keys, or in arrival order, with
+or without TRUST_SUMS) against tests/reassemble_model.py.  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -54,6 +57,7 @@ import coalesce_tunnel_model  # noqa: E402
 import fragment_model  # noqa: E402
 import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
+import reassemble_model  # noqa: E402
 import segment_chains_model  # noqa: E402
 import segment_model  # noqa: E402
 import segment_tunnel_chains_model  # noqa: E402
@@ -418,6 +422,37 @@ def check_fragment(rng, seed):
     return {"cfg": cfg, "n": int(hb.n), "mtu": mtu, "ignore_df": ignore_df, "n_out": int(totals[0])}
 
 
+def check_reassemble(rng, seed):
+    """rpkt_gpu_reassemble_keys and rpkt_gpu_reassemble_batch on the fragments of a generator
+    batch at a random mtu, shuffled, against tests/reassemble_model.py: the keys, then the
+    batch under the keys' order or in arrival order."""
+    cfg = int(rng.choice([4, 5, 6, 11, 12, 13, 14]))
+    src = segment_model.frames_of(gen.make_batch(cfg, int(rng.integers(1, 1500)), seed=seed))
+    mtu = int(rng.choice([28, 36, 48, 68, 100, 300, 576, 1280, 1500]))
+    hb, _ = reassemble_model.fragmented(src, mtu, True, int(rng.integers(0, 1 << 32)))
+    fr = segment_model.frames_of(hb)
+    hb = segment_model.pack([fr[k] for k in rng.permutation(len(fr))], lead=int(rng.integers(0, 16)))
+    recs = segment_model.oracle_records(hb)
+    trust, ordered = bool(rng.random() < 0.3), bool(rng.random() < 0.8)
+    db = engine.DeviceBatch.from_host(hb)
+    grecs = engine.parse_batch(db, segment_model.F6)
+    gk = engine.reassemble_keys(db, grecs, trust_sums=trust)
+    keys = reassemble_model.keys(hb, recs, trust)
+    assert np.array_equal(gk.cpu().numpy().view(np.uint64), keys), "reassemble_keys"
+    order = engine.reassemble_order(gk) if ordered else None
+    if ordered:
+        assert np.array_equal(order.cpu().numpy().view(np.uint32), reassemble_model.order_of(keys)), \
+            "reassemble_order"
+    out, first, totals = reassemble_model.reassemble(
+        hb, recs, reassemble_model.order_of(keys) if ordered else None, trust)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    odb, gf, gt = engine.reassemble_batch(db, grecs, order, trust, out_cap=out_cap,
+                                          out_bytes=int(totals[1]) + int(rng.integers(0, 40)))
+    same_reframed("reassemble_batch", odb, gf, gt, out, first, totals, out_cap)
+    return {"cfg": cfg, "n": int(hb.n), "mtu": mtu, "trust": trust, "ordered": ordered,
+            "n_src": len(src), "n_out": int(totals[0])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=8.0)
@@ -458,6 +493,8 @@ def main():
                 rec["segment_tunnel_chains"] = check_segment_tunnel_chains(rng, seed)
                 step = "fragment"
                 rec["fragment"] = check_fragment(rng, seed)
+                step = "reassemble"
+                rec["reassemble"] = check_reassemble(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")
