@@ -443,6 +443,18 @@ extern "C" {
                                    out_offsets_dev: *mut u32, out_cap: u32,
                                    frag_first_dev: *mut u32, totals_dev: *mut u64,
                                    workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_fragment_chains for n_chains (rpkt_gpu_fragment_batch's for as many
+    /// frames).
+    pub fn rpkt_gpu_fragment_chains_workspace_bytes(n_chains: u32) -> usize;
+    /// rpkt_gpu_fragment_batch over mbuf chains, read in place, located by
+    /// rpkt_gpu_parse_chains' records: every output is what the flat entry writes for the
+    /// chains' bytes in order; the output is a packed, flat batch.
+    pub fn rpkt_gpu_fragment_chains(chains: *const rpkt_chains_t, recs_dev: *const rpkt_rec_t,
+                                    mtu: u32, flags: u32, ip6_ident: u32,
+                                    out_frames_dev: *mut u8, out_bytes: u64,
+                                    out_offsets_dev: *mut u32, out_cap: u32,
+                                    frag_first_dev: *mut u32, totals_dev: *mut u64,
+                                    workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
     /// Workspace of rpkt_gpu_reassemble_batch for n positions.
     pub fn rpkt_gpu_reassemble_workspace_bytes(n: u32) -> usize;
     /// IPv4 / IPv6 reassembly on the device: consecutive positions, taken in `order_dev`'s order

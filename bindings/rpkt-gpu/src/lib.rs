@@ -569,6 +569,28 @@ pub unsafe fn fragment_batch(batch: &ffi::rpkt_batch_t, recs_dev: *const Rec, mt
                                        out.seg_first_dev, out.totals_dev, workspace_dev, stream))
 }
 
+/// rpkt_gpu_fragment_chains_workspace_bytes: the workspace of fragment_chains for `n_chains`.
+pub fn fragment_chains_workspace_bytes(n_chains: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_fragment_chains_workspace_bytes(n_chains) }
+}
+
+/// rpkt_gpu_fragment_chains: fragment_batch over mbuf chains, read in place (no gather into a
+/// flat batch first); `mtu`, `flags` and `ip6_ident` as there, `ip6_ident` + p the
+/// identification of chain p.  `out` is laid out as segment_batch's, with `seg_first_dev` the
+/// first fragment of every chain: the output is a packed, flat batch of wire frames.
+///
+/// # Safety
+/// As for `segment_chains`, with `workspace_dev` holding
+/// `fragment_chains_workspace_bytes(chains.n_chains)` bytes (16-byte aligned).
+pub unsafe fn fragment_chains(chains: &ffi::rpkt_chains_t, recs_dev: *const Rec, mtu: u32,
+                              flags: u32, ip6_ident: u32, out: &SegmentOut,
+                              workspace_dev: *mut core::ffi::c_void,
+                              stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_fragment_chains(chains, recs_dev, mtu, flags, ip6_ident, out.frames_dev,
+                                        out.out_bytes, out.offsets_dev, out.out_cap,
+                                        out.seg_first_dev, out.totals_dev, workspace_dev, stream))
+}
+
 /// rpkt_gpu_reassemble_workspace_bytes: the workspace of reassemble_batch for `n` positions.
 pub fn reassemble_workspace_bytes(n: u32) -> usize {
     unsafe { ffi::rpkt_gpu_reassemble_workspace_bytes(n) }

@@ -119,6 +119,9 @@ enum rpkt_status {
  *   rpkt_gpu_fragment_batch: rpkt_gpu_segment_batch's order with frag_first_dev in
  *     seg_first_dev's place, flags other than 0 or RPKT_FRAGMENT_IGNORE_DF, then mtu outside
  *     1..65535 in mss's place;
+ *   rpkt_gpu_fragment_chains: rpkt_gpu_segment_chains' order with frag_first_dev in
+ *     seg_first_dev's place, flags other than 0 or RPKT_FRAGMENT_IGNORE_DF, then mtu outside
+ *     1..65535 in mss's place;
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
@@ -1052,8 +1055,9 @@ int rpkt_gpu_segment_tunnel_chains(const rpkt_chains_t* chains, const rpkt_rec_t
  * A tunnelled frame is to this entry what its outer record says: the OUTER IP packet is
  * fragmented, which is what a VTEP does with an encapsulation that is over the MTU.
  * Argument checks: rpkt_gpu_segment_batch's in its order (at enum rpkt_err).
- * Not covered: fragmentation over mbuf chains; fragmenting the inner packet of a tunnel; an MTU
- * per frame.  The receive-side inverse is rpkt_gpu_reassemble_batch, below. */
+ * Over mbuf chains: rpkt_gpu_fragment_chains, below.
+ * Not covered: fragmenting the inner packet of a tunnel; an MTU per frame.  The receive-side
+ * inverse is rpkt_gpu_reassemble_batch, below. */
 #define RPKT_FRAGMENT_IGNORE_DF 1u   /* cut IPv4 packets that have DF set, too */
 
 size_t rpkt_gpu_fragment_workspace_bytes(uint32_t n);
@@ -1063,6 +1067,58 @@ int rpkt_gpu_fragment_batch(const rpkt_batch_t* batch, const rpkt_rec_t* recs_de
                             uint32_t* out_offsets_dev, uint32_t out_cap,
                             uint32_t* frag_first_dev, uint64_t* totals_dev,
                             void* workspace_dev, void* stream);
+
+/* The same over mbuf chains.  A packet that needs fragmenting is larger than the MTU, and in a
+ * DPDK port anything larger than one 2048-byte data room is a chain: every jumboframe_tx.rs
+ * frame, a VTEP's encapsulated jumbo frame whose outer packet is over the MTU.
+ * rpkt_gpu_fragment_chains reads the chains in place -- no gather into a flat batch first --
+ * and writes wire frames, which are linear by nature.
+ *
+ * Let F_p be chain p's bytes in order under rpkt_chains_t's clamps (a = min(chain_first[p],
+ * n_segs), b = min(max(chain_first[p+1], a), n_segs), each segment clamped to buf_bytes, empty
+ * segments contributing nothing).  Every output -- out_frames_dev, out_offsets_dev,
+ * frag_first_dev, totals_dev -- is byte for byte what rpkt_gpu_fragment_batch writes for the
+ * packed batch F_0 .. F_{n_chains-1} with the same recs_dev, mtu, flags, ip6_ident, out_cap and
+ * out_bytes: both rules (IPv4 with ip_options_fragment's NOOPs; IPv6 with the Fragment header
+ * and identification ip6_ident + p), the pass-through of every chain that is not cut as a copy
+ * of [0, pkt_len), the bytes after the IP packet's end dropped, the overflow contract, the
+ * spare offset slots, nothing written outside the buffers.
+ *   Records   recs_dev are normally rpkt_gpu_parse_chains' records of these chains
+ *             (RPKT_F_IPV6 for IPv6): their offsets are logical positions in F_p already.  A
+ *             header that straddles a segment boundary is a parse error there, so such a chain
+ *             passes through.  The entry itself puts no condition on where segments are cut:
+ *             with records that say "cut" (a parse of the flattened bytes), the IPv4 header
+ *             with its options, the IPv6 extension-header walk up to l4_off, the copied header
+ *             [0, l4_off) or [0, U) and the payload slices are gathered across any cuts.
+ *   Nesting   pkt_len, the sum of the clamped segment lengths, takes frame_len's place in
+ *             l3 + L <= frame_len and E <= frame_len.
+ *   Overlap   segments may overlap or be shared between chains: the arena is only read.
+ *   Huge      pkt_len is summed in 64 bits for totals_dev; a chain of 4 GiB or more cannot
+ *             fit out_bytes, so the call ends as an overflow.
+ *   Faults    every arena load goes through the buffer resource over [buf_dev, + buf_bytes)
+ *             and every store through one over the output: wrong records give wrong frames,
+ *             never a fault.
+ *   Limits    no cap on the segments of a chain (many tiny segments are slow, not wrong).
+ * flags: 0 or RPKT_FRAGMENT_IGNORE_DF.  workspace_dev:
+ * rpkt_gpu_fragment_chains_workspace_bytes(n_chains) bytes (equal to
+ * rpkt_gpu_fragment_workspace_bytes(n_chains)), 16-byte aligned; calls that share one must be
+ * ordered.  No host step: rpkt_gpu_parse_chains -> rpkt_gpu_fragment_chains ->
+ * rpkt_gpu_parse_batch over out_cap slots captures as one graph.
+ * Bounds for sizing: rpkt_gpu_fragment_batch's with the sum of the chains' pkt_len in
+ * frames_bytes' place; that sum is at most buf_bytes when segments do not overlap.
+ * A tunnelled chain is to this entry what its outer record says: with the outer records of
+ * rpkt_gpu_parse_tunnel_chains the OUTER IP packet is fragmented.
+ * Argument checks: rpkt_gpu_segment_chains' in its order, with mtu in mss's place and
+ * RPKT_FRAGMENT_IGNORE_DF the only flag (at enum rpkt_err).
+ * Not covered: what rpkt_gpu_fragment_batch does not cover; reassembly or coalescing over
+ * chains; a chain-shaped output. */
+size_t rpkt_gpu_fragment_chains_workspace_bytes(uint32_t n_chains);
+int rpkt_gpu_fragment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs_dev, uint32_t mtu,
+                             uint32_t flags, uint32_t ip6_ident,
+                             uint8_t* out_frames_dev, uint64_t out_bytes,
+                             uint32_t* out_offsets_dev, uint32_t out_cap,
+                             uint32_t* frag_first_dev, uint64_t* totals_dev,
+                             void* workspace_dev, void* stream);
 
 /* ---- IPv4 / IPv6 reassembly --------------------------------------------------------- */
 

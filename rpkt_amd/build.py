@@ -29,7 +29,7 @@ GPU_SRC = [os.path.join(HERE, "csrc", f) for f in
             "rpkt_fragment.hip", "rpkt_reassemble.hip", "rpkt_abi.hip", "rpkt_coll.hip")]
 GPU_DEPS = [os.path.join(HERE, "csrc", h) for h in
             ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h", "rpkt_chain.h", "rpkt_tunnel.h",
-             "rpkt_segcopy.h", "rpkt_proto_table.h")]                 # included; the table is generated
+             "rpkt_segcopy.h", "rpkt_chaincopy.h", "rpkt_proto_table.h")]                 # included; the table is generated
 # units compiled a second time with other defines (same source: same unit hash)
 SECOND_COMPILES = [("rpkt_tx.hip", "rpkt_tx_w64.o", ["-DRPKT_WIN=64", "-DRPKT_TX_W64"]),
                    # only the compact parse of short strided frames: the unit's other
@@ -49,9 +49,11 @@ UNIT_HEADERS = {"rpkt_parse.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_opts.h"
                 "rpkt_tunnel_chains.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_chain.h",
                                            "rpkt_tunnel.h"),
                 "rpkt_tunnel_next.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_tunnel.h"),
-                "rpkt_segment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
+                "rpkt_segment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h",
+                                     "rpkt_chaincopy.h"),
                 "rpkt_coalesce.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
-                "rpkt_fragment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
+                "rpkt_fragment.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h",
+                                      "rpkt_chaincopy.h"),
                 "rpkt_reassemble.hip": ("rpkt_common.h", "rpkt_args.h", "rpkt_segcopy.h"),
                 "rpkt_abi.hip": ("rpkt_common.h",),
                 "rpkt_coll.hip": ("rpkt_common.h",)}
@@ -136,7 +138,8 @@ def build_gen(force=False):
 
 
 EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "tso_tx_chains", "lro_rx",
-            "vtep_tx", "vtep_gro_rx", "vtep_tx_chains", "vtep_frag_tx", "vtep_frag_rx")
+            "vtep_tx", "vtep_gro_rx", "vtep_tx_chains", "vtep_frag_tx", "vtep_frag_rx",
+            "frag_tx_chains")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "parse_batch")
 FLOW_REDUCE_BIN = os.path.join(ROOT, "examples", "flow_reduce")
 VTEP_RX_BIN = os.path.join(ROOT, "examples", "vtep_rx")
@@ -148,6 +151,7 @@ VTEP_GRO_RX_BIN = os.path.join(ROOT, "examples", "vtep_gro_rx")
 VTEP_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "vtep_tx_chains")
 VTEP_FRAG_TX_BIN = os.path.join(ROOT, "examples", "vtep_frag_tx")
 VTEP_FRAG_RX_BIN = os.path.join(ROOT, "examples", "vtep_frag_rx")
+FRAG_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "frag_tx_chains")
 
 
 def build_example(force=False):

@@ -27,11 +27,23 @@
 // Every load goes through the frames buffer resource and every store through one over
 // [out_frames_dev, + out_bytes); an overflowing batch writes its totals and frag_first and
 // nothing else.  A record whose offsets do not nest makes its frame pass through.
-#include "rpkt_segcopy.h"
+//
+// rpkt_gpu_fragment_chains is the same cut over mbuf chains (rpkt_chains_t), the frame being the
+// chain's bytes in order, put together from rpkt_chaincopy.h as rpkt_gpu_segment_chains is
+// (rpkt_segment.hip has the description): a plan and a write kernel of its own, everything
+// else shared, the scan kernels included.  The plan's lane walks its chain's segments for
+// pkt_len and the first non-empty segment, and reads the header [0, l4_off) as a flat frame's
+// when it lies in that segment (the mbuf layout, and nearly every chain rpkt_gpu_parse_chains
+// accepts) and byte by byte through the segment list otherwise; the rules are the ones above,
+// templated on the header reader.  The write copies each slice as one wave copy per segment it
+// touches and carries its place in the segment list from one fragment of a chain to the next:
+// slices ascend, so the cursor only moves forward.
+#include "rpkt_chaincopy.h"
 
 namespace {
 
-// plan words: 0 frame offset, 1 frame length, 2 l3 | hs << 16 (hs: the header bytes copied from
+// plan words: 0 frame offset (chains: the chain's first segment, clamped), 1 frame length
+// (chains: pkt_len), 2 l3 | hs << 16 (hs: the header bytes copied from
 // the frame, l4_off for IPv4 and U for IPv6), 3 c | P << 16 (P: the bytes all the fragments
 // carry together), 7 bit 0 cut, bit 1 IPv6;
 //   IPv4: 4 header sum with the original options | with the NOOP-ed ones << 16, 5 the frame's
@@ -52,7 +64,8 @@ __device__ __forceinline__ uint32_t nibble_bytes(uint32_t m) {
 
 // The IPv4 rule for the frame at H (record offsets l3, l4; len: the frame's length): true when
 // it is cut, then cnt fragments and their bytes, plan words 2..7.
-__device__ __forceinline__ bool plan_ip4(const FlatHeader& H, uint32_t l3, uint32_t l4, uint32_t len,
+template <class Header>
+__device__ __forceinline__ bool plan_ip4(const Header& H, uint32_t l3, uint32_t l4, uint32_t len,
                                          uint32_t mtu, bool ignore_df, uint32_t (&p)[8],
                                          uint64_t& cnt, uint64_t& bytes) {
     const uint32_t ip0 = H.dw(l3), ip1 = H.dw(l3 + 4u);
@@ -100,7 +113,8 @@ __device__ __forceinline__ bool plan_ip4(const FlatHeader& H, uint32_t l3, uint3
 }
 
 // The IPv6 rule, likewise; ident: the Fragment header's identification for this frame.
-__device__ __forceinline__ bool plan_ip6(const FlatHeader& H, uint32_t l3, uint32_t l4, uint32_t len,
+template <class Header>
+__device__ __forceinline__ bool plan_ip6(const Header& H, uint32_t l3, uint32_t l4, uint32_t len,
                                          uint32_t mtu, uint32_t ident, uint32_t (&p)[8],
                                          uint64_t& cnt, uint64_t& bytes) {
     const uint32_t ip1 = H.dw(l3 + 4u);
@@ -139,6 +153,22 @@ __device__ __forceinline__ bool plan_ip6(const FlatHeader& H, uint32_t l3, uint3
     return true;
 }
 
+// What a staged record says about a frame: which rule applies and the offsets it reads.
+struct FragWhere {
+    bool v4, v6;
+    uint32_t l3, l4;
+};
+__device__ __forceinline__ FragWhere frag_where(const uint32_t* w) {
+    const uint32_t w0 = w[0], w5 = w[5], w16 = w[16];
+    const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
+    const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
+    // the statuses under which the IP header parsed (IPv6: and its extension headers)
+    const bool l4_status = status == RPKT_S_OK ||
+                           (status >= RPKT_S_L4_OTHER && status <= RPKT_S_TCP_BAD_DOFF);
+    return FragWhere{det == 0x0800u && (l4_status || status == RPKT_S_ICMP_EMPTY),
+                     det == 0x86ddu && l4_status, w16 & 0xffffu, w16 >> 16};
+}
+
 __global__ __launch_bounds__(kSegBlock)
 void fragment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
                           const uint32_t* __restrict__ offsets, uint32_t stride, uint32_t frame_len,
@@ -165,37 +195,27 @@ void fragment_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
         if (valid) {
             cnt = 1;
             bytes = fr.len;
-            const uint32_t w0 = w[0], w5 = w[5], w16 = w[16];
-            const uint32_t status = w0 & 0xffu, nv = (w0 >> 8) & 0xffu;
-            const uint32_t det = nv == 0u ? w0 >> 16 : (nv == 1u ? w5 & 0xffffu : w5 >> 16);
-            const uint32_t l3 = w16 & 0xffffu, l4 = w16 >> 16;
-            // the statuses under which the IP header parsed (IPv6: and its extension headers)
-            const bool l4_status = status == RPKT_S_OK ||
-                                   (status >= RPKT_S_L4_OTHER && status <= RPKT_S_TCP_BAD_DOFF);
+            const FragWhere f = frag_where(w);
             const FlatHeader H{make_rsrc(frames, fb), fb, fr.off};
-            if (det == 0x0800u && (l4_status || status == RPKT_S_ICMP_EMPTY))
-                plan_ip4(H, l3, l4, fr.len, mtu, ignore_df != 0u, p, cnt, bytes);
-            else if (det == 0x86ddu && l4_status)
-                plan_ip6(H, l3, l4, fr.len, mtu, ip6_ident + i, p, cnt, bytes);
+            if (f.v4)
+                plan_ip4(H, f.l3, f.l4, fr.len, mtu, ignore_df != 0u, p, cnt, bytes);
+            else if (f.v6)
+                plan_ip6(H, f.l3, f.l4, fr.len, mtu, ip6_ident + i, p, cnt, bytes);
         }
     }
     plan_store(valid, i, p, cnt, bytes, plan, frag_first, obase, part, red);
 }
 
-// Output j, fragment k of the input frame with plan (pa, pb) and output byte base `base`: its
-// offset entry and its bytes, the whole wave.
-__device__ __forceinline__ void write_fragment(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
-                                               __amdgpu_buffer_rsrc_t ro,
-                                               uint32_t* __restrict__ out_offsets, uint32_t j,
-                                               uint32_t k, u32x4 pa, u32x4 pb, uint32_t base,
-                                               int lane) {
-    const uint32_t foff = pa.x, flen = pa.y;
-    if (!(pb.w & kFragOn)) {                                      // pass-through: a byte copy
-        if (lane == 0) out_offsets[j + 1] = base + flen;
-        wave_copy<false>(rs, fb, ro, foff, base, flen, lane);
-        return;
-    }
-    const bool v6 = (pb.w & kFragV6) != 0u;                       // wave-uniform, as all below
+// Fragment k of a cut frame with plan (pa, pb) and output byte base `base`: where it goes
+// (d0), the H bytes before its slice (hs of them the frame's), the slice [done, + pk) of the
+// bytes after the frame's hs, the header's patches (Pt) and its NOOP mask.  Wave-uniform.
+struct FragOut {
+    uint32_t l3, hs, H, done, pk, d0;
+    uint64_t mask;
+};
+__device__ __forceinline__ FragOut frag_out(u32x4 pa, u32x4 pb, uint32_t k, uint32_t base,
+                                            SegPatch (&Pt)[kFragPatches]) {
+    const bool v6 = (pb.w & kFragV6) != 0u;
     const uint32_t l3 = pa.z & 0xffffu, hs = pa.z >> 16, c = pa.w & 0xffffu, P = pa.w >> 16;
     const uint32_t H = v6 ? hs + 8u : hs;                         // the bytes before the slice
     const uint32_t done = k * c;                                  // < P: k < ceil(P / c)
@@ -203,9 +223,6 @@ __device__ __forceinline__ void write_fragment(__amdgpu_buffer_rsrc_t rs, uint32
     const uint32_t pk = left < c ? left : c;
     const bool last = left <= c;
     const uint32_t d0 = base + k * (H + c);
-    if (lane == 0) out_offsets[j + 1] = d0 + H + pk;
-
-    SegPatch Pt[kFragPatches];
     const uint64_t mask = (v6 || k == 0u) ? 0ull : ((uint64_t)(pb.y >> 16) << 32) | pb.z;
     if (!v6) {
         const uint32_t fw0 = pb.y & 0xffffu;
@@ -224,22 +241,44 @@ __device__ __forceinline__ void write_fragment(__amdgpu_buffer_rsrc_t rs, uint32
         Pt[2] = SegPatch{hs, 4u, nh | (bswap16(done | (last ? 0u : 1u)) << 16)};
         Pt[3] = SegPatch{hs + 4u, 4u, bswap32(pb.y)};
     }
-    // the header's source bytes of destination dword q, the NOOP mask applied: the dword's
-    // byte b is option byte rel + b - (l3 + 20)
-    auto fetch = [&](uint32_t q) -> uint32_t {
-        uint32_t v = header_dword(rs, fb, foff, d0, q);
-        if (mask != 0ull) {
-            const int o = (int)((d0 & ~3u) + 4u * q - d0) - (int)(l3 + 20u);
-            if (o > -4 && o < 40) {
-                const uint32_t bm = nibble_bytes((uint32_t)(o >= 0 ? mask >> o : mask << -o) & 0xfu);
-                v = (v & ~bm) | (0x01010101u & bm);
-            }
+    return FragOut{l3, hs, H, done, pk, d0, mask};
+}
+
+// The header's source bytes v of destination dword q with the NOOP mask applied: the dword's
+// byte b is option byte rel + b - (l3 + 20)
+__device__ __forceinline__ uint32_t noop_dword(const FragOut& o, uint32_t q, uint32_t v) {
+    if (o.mask != 0ull) {
+        const int x = (int)((o.d0 & ~3u) + 4u * q - o.d0) - (int)(o.l3 + 20u);
+        if (x > -4 && x < 40) {
+            const uint32_t bm = nibble_bytes((uint32_t)(x >= 0 ? o.mask >> x : o.mask << -x) & 0xfu);
+            v = (v & ~bm) | (0x01010101u & bm);
         }
-        return v;
+    }
+    return v;
+}
+
+// Output j, fragment k of the input frame with plan (pa, pb) and output byte base `base`: its
+// offset entry and its bytes, the whole wave.
+__device__ __forceinline__ void write_fragment(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                               __amdgpu_buffer_rsrc_t ro,
+                                               uint32_t* __restrict__ out_offsets, uint32_t j,
+                                               uint32_t k, u32x4 pa, u32x4 pb, uint32_t base,
+                                               int lane) {
+    const uint32_t foff = pa.x, flen = pa.y;
+    if (!(pb.w & kFragOn)) {                                      // pass-through: a byte copy
+        if (lane == 0) out_offsets[j + 1] = base + flen;
+        wave_copy<false>(rs, fb, ro, foff, base, flen, lane);
+        return;
+    }
+    SegPatch Pt[kFragPatches];
+    const FragOut o = frag_out(pa, pb, k, base, Pt);              // wave-uniform
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.H + o.pk;
+    auto fetch = [&](uint32_t q) -> uint32_t {
+        return noop_dword(o, q, header_dword(rs, fb, foff, o.d0, q));
     };
     const uint32_t hfirst = fetch((uint32_t)lane);
-    wave_copy<false>(rs, fb, ro, foff + hs + done, d0 + H, pk, lane);
-    wave_copy_header_from(ro, d0, H, hfirst, Pt, lane, fetch);
+    wave_copy<false>(rs, fb, ro, foff + o.hs + o.done, o.d0 + o.H, o.pk, lane);
+    wave_copy_header_from(ro, o.d0, o.H, hfirst, Pt, lane, fetch);
 }
 
 __global__ __launch_bounds__(kSegBlock)
@@ -271,6 +310,153 @@ void fragment_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint
     }
 }
 
+// ---- mbuf chains -------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kSegBlock)
+void fragment_chains_plan_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
+                                 const uint32_t* __restrict__ segs, uint32_t n_segs,
+                                 const uint32_t* __restrict__ chain_first, uint32_t n,
+                                 const rpkt_rec_t* __restrict__ recs, uint32_t mtu,
+                                 uint32_t ignore_df, uint32_t ip6_ident, u32x4* __restrict__ plan,
+                                 uint32_t* __restrict__ frag_first, uint64_t* __restrict__ obase,
+                                 uint64_t* __restrict__ part) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    uint64_t cnt = 0, bytes = 0;
+    uint32_t p[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+
+    if (p0 < n) {                                                 // wave-uniform
+        uint32_t* st = stage[wave];
+        stage_records_tile(st, recs, p0, n, lane);
+        const SegTable S{segs, fb};
+        // pkt_len in 64 bits (segments may overlap: no bound but n_segs * buf_bytes), and the
+        // first non-empty segment, where the header starts
+        uint32_t a = 0, b = 0;
+        if (valid) chain_range(chain_first, n_segs, i, a, b);
+        uint64_t pkt = 0;
+        Frame s0{fb, 0u};
+        for (uint32_t k = a; k < b; ++k) {
+            const Frame s = S.seg(k);
+            if (pkt == 0) s0 = s;
+            pkt += s.len;
+        }
+        // a chain of 4 GiB or more cannot fit out_bytes: the call overflows and the write
+        // never sees this plan; the IP lengths are 16 bits wide, so saturating is exact
+        const uint32_t len = pkt < 0xffffffffull ? (uint32_t)pkt : 0xffffffffu;
+        p[0] = a;
+        p[1] = len;
+        if (valid) {
+            cnt = 1;
+            bytes = pkt;
+            const FragWhere f = frag_where(st + lane * 21);
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
+            if (f.v4 || f.v6) {
+                if (__builtin_expect(f.l4 <= s0.len, 1)) {
+                    const FlatHeader H{rs, fb, s0.off};
+                    if (f.v4) plan_ip4(H, f.l3, f.l4, len, mtu, ignore_df != 0u, p, cnt, bytes);
+                    else plan_ip6(H, f.l3, f.l4, len, mtu, ip6_ident + i, p, cnt, bytes);
+                } else {
+                    const GatheredHeader H{S, rs, a, b, f.l4};
+                    if (f.v4) plan_ip4(H, f.l3, f.l4, len, mtu, ignore_df != 0u, p, cnt, bytes);
+                    else plan_ip6(H, f.l3, f.l4, len, mtu, ip6_ident + i, p, cnt, bytes);
+                }
+            }
+        }
+    }
+    plan_store(valid, i, p, cnt, bytes, plan, frag_first, obase, part, red);
+}
+
+// The chain a wave is writing fragments of: its plan, its output byte base, the cursor, and
+// where the header is (hdr: the first non-empty segment's offset when the copied header
+// [0, hs) lies in it, `flat`).
+struct FragChainState {
+    u32x4 pa, pb;
+    uint32_t base, hdr;
+    bool flat;
+    ChainCursor c;
+};
+__device__ __forceinline__ FragChainState frag_chain_state(const u32x4* __restrict__ plan,
+                                                           const uint64_t* __restrict__ obase,
+                                                           uint32_t i, const SegTable& S,
+                                                           uint32_t n_segs) {
+    FragChainState st;
+    st.pa = plan[2 * (size_t)i];
+    st.pb = plan[2 * (size_t)i + 1];
+    st.base = (uint32_t)obase[i];                                 // < need <= out_bytes < 4 GiB
+    st.c = ChainCursor{st.pa.x, 0u};
+    st.hdr = S.fb;
+    st.flat = true;
+    if (st.pb.w & kFragOn) {                            // pkt_len >= hs > 0: a segment has bytes
+        Frame s{S.fb, 0u};
+        while (st.c.k < n_segs && (s = S.seg(st.c.k)).len == 0u) ++st.c.k;
+        st.hdr = s.off;
+        st.flat = (st.pa.z >> 16) <= s.len;
+    }
+    return st;
+}
+
+// write_fragment over a chain: the slice and the pass-through copy through the cursor, the
+// header from the first non-empty segment or gathered
+__device__ __forceinline__ void write_chain_fragment(__amdgpu_buffer_rsrc_t rs, const SegTable& S,
+                                                     uint32_t n_segs, __amdgpu_buffer_rsrc_t ro,
+                                                     uint32_t* __restrict__ out_offsets, uint32_t j,
+                                                     uint32_t k, FragChainState& st, int lane) {
+    const uint32_t fb = S.fb;
+    if (!(st.pb.w & kFragOn)) {                                   // pass-through: a byte copy
+        if (lane == 0) out_offsets[j + 1] = st.base + st.pa.y;
+        chain_copy<false>(rs, S, n_segs, ro, st.c, 0u, st.base, st.pa.y, lane);
+        return;
+    }
+    SegPatch Pt[kFragPatches];
+    const FragOut o = frag_out(st.pa, st.pb, k, st.base, Pt);     // wave-uniform
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.H + o.pk;
+    // IPv6: the 8 bytes after [0, hs) are the Fragment header's, all of them patched
+    const GatheredHeader G{S, rs, st.pa.x, n_segs, o.hs};
+    const uint32_t hdr = st.hdr;
+    const bool flat = st.flat;                                    // wave-uniform
+    auto fetch = [&](uint32_t q) -> uint32_t {
+        return noop_dword(o, q, flat ? header_dword(rs, fb, hdr, o.d0, q)
+                                     : G.dw((o.d0 & ~3u) + 4u * q - o.d0));
+    };
+    const uint32_t hfirst = fetch((uint32_t)lane);
+    chain_copy<false>(rs, S, n_segs, ro, st.c, o.hs + o.done, o.d0 + o.H, o.pk, lane);
+    wave_copy_header_from(ro, o.d0, o.H, hfirst, Pt, lane, fetch);
+}
+
+__global__ __launch_bounds__(kSegBlock)
+void fragment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
+                                  const uint32_t* __restrict__ segs, uint32_t n_segs, uint32_t n,
+                                  const u32x4* __restrict__ plan,
+                                  const uint32_t* __restrict__ frag_first,
+                                  const uint64_t* __restrict__ obase,
+                                  const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
+                                  uint32_t out_bytes, uint32_t* __restrict__ out_offsets,
+                                  uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t j0, jend, i;
+    if (!output_run(n, frag_first, totals, out_bytes, out_offsets, out_cap, lane, j0, jend, i)) return;
+    uint32_t cur = frag_first[i], nxt = frag_first[i + 1];
+    const SegTable S{segs, fb};
+    FragChainState st = frag_chain_state(plan, obase, i, S, n_segs);
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(buf, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t j = j0; j < jend; ++j) {
+        if (j >= nxt) {                                           // the next chain's first output
+            while (j >= nxt && i + 1u < n) {
+                ++i;
+                cur = nxt;
+                nxt = frag_first[i + 1];
+            }
+            st = frag_chain_state(plan, obase, i, S, n_segs);
+        }
+        write_chain_fragment(rs, S, n_segs, ro, out_offsets, j, j - cur, st, lane);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -295,6 +481,31 @@ int rpkt_gpu_fragment_batch(const rpkt_batch_t* b, const rpkt_rec_t* recs_dev, u
                           (hipStream_t)stream, b->frames_dev, (uint32_t)b->frames_bytes, b->n,
                           ws.plan, frag_first_dev, ws.obase, totals_dev, out_frames_dev,
                           (uint32_t)out_bytes, out_offsets_dev, out_cap);
+}
+
+size_t rpkt_gpu_fragment_chains_workspace_bytes(uint32_t n) { return seg_ws(nullptr, n).bytes; }
+
+int rpkt_gpu_fragment_chains(const rpkt_chains_t* c, const rpkt_rec_t* recs_dev, uint32_t mtu,
+                             uint32_t flags, uint32_t ip6_ident, uint8_t* out_frames_dev,
+                             uint64_t out_bytes, uint32_t* out_offsets_dev, uint32_t out_cap,
+                             uint32_t* frag_first_dev, uint64_t* totals_dev, void* workspace_dev,
+                             void* stream) {
+    RPKT_TRY(reframe_args_ok(c, recs_dev, mtu, flags, RPKT_FRAGMENT_IGNORE_DF, out_frames_dev,
+                             out_bytes, out_offsets_dev, out_cap, frag_first_dev, totals_dev,
+                             workspace_dev));
+    if (c->n_chains == 0) return RPKT_OK;
+
+    const uint32_t n = c->n_chains, fb = (uint32_t)c->buf_bytes;
+    const uint32_t* segs = c->segs_dev;
+    const SegWs ws = seg_ws(workspace_dev, n);
+    RPKT_TRY(launch(fragment_chains_plan_kernel, dim3(blocks(n)), dim3(kSegBlock), 0,
+                    (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, c->chain_first_dev, n,
+                    recs_dev, mtu, flags & RPKT_FRAGMENT_IGNORE_DF, ip6_ident, ws.plan,
+                    frag_first_dev, ws.obase, ws.part));
+    return scan_and_write(fragment_chains_write_kernel, ws, n, out_cap, frag_first_dev, totals_dev,
+                          (hipStream_t)stream, c->buf_dev, fb, segs, c->n_segs, n, ws.plan,
+                          frag_first_dev, ws.obase, totals_dev, out_frames_dev, (uint32_t)out_bytes,
+                          out_offsets_dev, out_cap);
 }
 
 }  // extern "C"

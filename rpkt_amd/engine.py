@@ -95,6 +95,9 @@ ABI = {
     "rpkt_gpu_fragment_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_fragment_batch": (_i, [_B, _p, _u32, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                      _p, _p]),
+    "rpkt_gpu_fragment_chains_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_fragment_chains": (_i, [_C, _p, _u32, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
+                                      _p, _p]),
     "rpkt_gpu_reassemble_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_reassemble_batch": (_i, [_B, _p, _p, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
                                        _p]),
@@ -788,18 +791,50 @@ def fragment_batch(batch, recs, mtu, ignore_df=False, ip6_ident=0, out_frames=No
     header of the batch (IPv4: ihl; IPv6: 40 and the extension headers up to the last Routing
     header), and out_bytes = frames_bytes + (out_cap - n) * (22 + l3_header_max + 8) bytes:
     Ethernet with two tags, that header and a Fragment header before each further slice."""
-    n, fbytes = batch.n, batch.frames.numel()
+    return _fragment("rpkt_gpu_fragment_batch", batch, "fragment_batch", recs, mtu, ignore_df,
+                     ip6_ident, out_frames, out_offsets, out_cap, out_bytes, frag_first, totals,
+                     workspace, l3_header_max, stream)
+
+
+def _fragment(name, src, what, recs, mtu, ignore_df, ip6_ident, out_frames, out_offsets, out_cap,
+              out_bytes, frag_first, totals, workspace, l3_header_max, stream):
+    """fragment_batch and fragment_chains: `src` (a DeviceBatch or DeviceChains) cut at `mtu`
+    into a packed DeviceBatch; the default sizes from the documented bound over src's bytes."""
+    n, fbytes = src.n, src.frames.numel()
     out_frames, out_bytes, out_offsets, out_cap, frag_first, totals, workspace = _reframe_outputs(
-        "fragment_batch", batch, recs,
+        what, src, recs,
         lambda: n + fbytes // max(8, (mtu - l3_header_max - 8) & ~7),
         lambda cap: fbytes + (cap - n) * (22 + l3_header_max + 8),
         out_frames, out_offsets, out_cap, out_bytes, frag_first, "frag_first", totals, workspace,
         "fragment")
-    _call("rpkt_gpu_fragment_batch", ctypes.byref(batch.desc()), recs.data_ptr(), mtu,
+    _call(name, ctypes.byref(src.desc()), recs.data_ptr(), mtu,
           FRAGMENT_IGNORE_DF if ignore_df else 0, ip6_ident & 0xffffffff, out_frames.data_ptr(),
           out_bytes, out_offsets.data_ptr(), out_cap, frag_first.data_ptr(), totals.data_ptr(),
           workspace.data_ptr(), _stream_ptr(stream))
     return DeviceBatch(out_frames, out_cap, out_offsets), frag_first, totals
+
+
+def fragment_chains_workspace(n, device="cuda"):
+    """The workspace tensor of fragment_chains for n chains
+    (rpkt_gpu_fragment_chains_workspace_bytes)."""
+    return _workspace("fragment_chains", n, device)
+
+
+def fragment_chains(chains, recs, mtu, ignore_df=False, ip6_ident=0, out_frames=None,
+                    out_offsets=None, out_cap=None, out_bytes=None, frag_first=None, totals=None,
+                    workspace=None, l3_header_max=60, stream=None):
+    """rpkt_gpu_fragment_chains: fragment_batch over mbuf chains (a DeviceChains), read in place;
+    `recs` are parse_chains' records of them (with F_IPV6 for IPv6 chains to be cut), ignore_df
+    and ip6_ident as for fragment_batch.  The same return value: (out, frag_first, totals), `out`
+    a packed, flat DeviceBatch of wire frames.  The default sizes are fragment_batch's with the
+    arena's size, chains.buf.numel(), for frames_bytes: that bounds the chains' bytes only when
+    segments do not overlap and are not shared between chains; size the outputs yourself
+    otherwise."""
+    if workspace is None:
+        workspace = fragment_chains_workspace(chains.n, chains.buf.device)
+    return _fragment("rpkt_gpu_fragment_chains", chains, "fragment_chains", recs, mtu, ignore_df,
+                     ip6_ident, out_frames, out_offsets, out_cap, out_bytes, frag_first, totals,
+                     workspace, l3_header_max, stream)
 
 
 REASSEMBLE_TRUST_SUMS = 1

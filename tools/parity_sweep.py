@@ -34,7 +34,10 @@ fuzz or tunnel configs) through rpkt_gpu_fragment_batch at a random mtu, with or
 RPKT_FRAGMENT_IGNORE_DF and with a random ip6_ident, against tests/fragment_model.py; (g) the
 model's fragments of such a batch at a random mtu, shuffled, through rpkt_gpu_reassemble_keys and
 rpkt_gpu_reassemble_batch (under engine.reassemble_order of the keys, or in arrival order, with
-or without TRUST_SUMS) against tests/reassemble_model.py.  Build and forward rewrite frames in place, so they run on generator batches
+or without TRUST_SUMS) against tests/reassemble_model.py; (h) a generator chain batch in the
+fuzz or the mbuf layout through rpkt_gpu_fragment_chains at a random mtu, flag and ip6_ident, with
+the chain parse's records or the flat ones of the flattened bytes, against
+tests/fragment_chains_model.py (the fragment model on the flattened chains).  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -54,6 +57,7 @@ from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_recor
                               as_records16, as_tunnels, project16)
 
 import coalesce_tunnel_model  # noqa: E402
+import fragment_chains_model  # noqa: E402
 import fragment_model  # noqa: E402
 import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
@@ -453,6 +457,29 @@ def check_reassemble(rng, seed):
             "n_src": len(src), "n_out": int(totals[0])}
 
 
+def check_fragment_chains(rng, seed):
+    """rpkt_gpu_fragment_chains on a generator chain batch in the fuzz or the mbuf layout at a
+    random mtu, with or without RPKT_FRAGMENT_IGNORE_DF, against the model on the flattened
+    chains."""
+    import torch
+    layout = "fuzz" if rng.random() < 0.6 else "mbuf"
+    cfg = int(rng.choice([5, 6, 8, 11, 12] if layout == "fuzz" else [7, 11]))
+    hc = gen.make_chains(cfg, n=int(rng.integers(1, 3000)), layout=layout, seed=seed)
+    mtu = int(rng.choice([28, 29, 36, 48, 68, 100, 300, 576, 1280, 1500, 65535]))
+    ignore_df, ident = bool(rng.random() < 0.7), int(rng.integers(0, 1 << 32))
+    kind = "chain" if rng.random() < 0.6 else "flat"
+    recs = fragment_chains_model.RECORDS[kind](hc)
+    out, first, totals = fragment_chains_model.fragment_chains(hc, recs, mtu, ignore_df, ident)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    d = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).copy()).cuda()
+    odb, gf, gt = engine.fragment_chains(engine.DeviceChains.from_host(hc), d, mtu, ignore_df, ident,
+                                         out_cap=out_cap,
+                                         out_bytes=int(totals[1]) + int(rng.integers(0, 40)))
+    same_reframed("fragment_chains", odb, gf, gt, out, first, totals, out_cap)
+    return {"cfg": cfg, "layout": layout, "n": int(hc.n), "mtu": mtu, "ignore_df": ignore_df,
+            "records": kind, "n_out": int(totals[0])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=8.0)
@@ -495,6 +522,8 @@ def main():
                 rec["fragment"] = check_fragment(rng, seed)
                 step = "reassemble"
                 rec["reassemble"] = check_reassemble(rng, seed)
+                step = "fragment_chains"
+                rec["fragment_chains"] = check_fragment_chains(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")
