@@ -79,6 +79,9 @@ pub const RPKT_COALESCE_UDP: u32 = 16;
 pub const RPKT_SEGMENT_UDP: u32 = 16;
 /// rpkt_gpu_fragment_batch: cut IPv4 packets that have DF set, too
 pub const RPKT_FRAGMENT_IGNORE_DF: u32 = 1;
+/// rpkt_gpu_fragment_tunnel_batch: a tunnelled frame whose inner packet is not cut: cut its
+/// outer packet
+pub const RPKT_FRAGMENT_TUNNEL_OUTER: u32 = 2;
 /// rpkt_gpu_reassemble_batch / _keys: do not require a valid IPv4 header sum
 pub const RPKT_REASSEMBLE_TRUST_SUMS: u32 = 1;
 
@@ -455,6 +458,21 @@ extern "C" {
                                     out_offsets_dev: *mut u32, out_cap: u32,
                                     frag_first_dev: *mut u32, totals_dev: *mut u64,
                                     workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Workspace of rpkt_gpu_fragment_tunnel_batch for n input frames.
+    pub fn rpkt_gpu_fragment_tunnel_workspace_bytes(n: u32) -> usize;
+    /// Fragmentation of the inner IPv4 packet of VXLAN, GTP-U and GRE frames before the
+    /// encapsulation (RFC 4459 section 3.2), located by rpkt_gpu_parse_tunnel_batch's three
+    /// record arrays: every output's outer IP packet is at most `mtu` long and has outer
+    /// headers of its own.  Frames without a tunnel are cut as rpkt_gpu_fragment_batch cuts
+    /// them; with RPKT_FRAGMENT_TUNNEL_OUTER so is a tunnelled frame whose inner packet is not
+    /// cut.
+    pub fn rpkt_gpu_fragment_tunnel_batch(batch: *const rpkt_batch_t, outer_dev: *const rpkt_rec_t,
+                                          tun_dev: *const rpkt_tun_t, inner_dev: *const rpkt_rec_t,
+                                          mtu: u32, flags: u32, ip6_ident: u32,
+                                          out_frames_dev: *mut u8, out_bytes: u64,
+                                          out_offsets_dev: *mut u32, out_cap: u32,
+                                          frag_first_dev: *mut u32, totals_dev: *mut u64,
+                                          workspace_dev: *mut c_void, stream: *mut c_void) -> c_int;
     /// Workspace of rpkt_gpu_reassemble_batch for n positions.
     pub fn rpkt_gpu_reassemble_workspace_bytes(n: u32) -> usize;
     /// IPv4 / IPv6 reassembly on the device: consecutive positions, taken in `order_dev`'s order

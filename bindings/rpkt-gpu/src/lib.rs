@@ -591,6 +591,34 @@ pub unsafe fn fragment_chains(chains: &ffi::rpkt_chains_t, recs_dev: *const Rec,
                                         out.seg_first_dev, out.totals_dev, workspace_dev, stream))
 }
 
+/// rpkt_gpu_fragment_tunnel_workspace_bytes: the workspace of fragment_tunnel_batch for `n`
+/// input frames.
+pub fn fragment_tunnel_workspace_bytes(n: u32) -> usize {
+    unsafe { ffi::rpkt_gpu_fragment_tunnel_workspace_bytes(n) }
+}
+
+/// rpkt_gpu_fragment_tunnel_batch: fragmentation of the inner IPv4 packet of the VXLAN / GTP-U /
+/// GRE frames of a batch before the encapsulation, so that every output's outer IP packet is at
+/// most `mtu` (1..65535) long, the outer lengths and checksums fixed up; frames without a tunnel
+/// are cut as fragment_batch cuts them.  `flags`: any of `ffi::RPKT_FRAGMENT_IGNORE_DF` and
+/// `ffi::RPKT_FRAGMENT_TUNNEL_OUTER` (a tunnelled frame whose inner packet is not cut has its
+/// outer packet cut instead of passing through); `ip6_ident` as for fragment_batch.  `out` is
+/// laid out as segment_batch's, with `seg_first_dev` the first fragment of every input frame.
+///
+/// # Safety
+/// As for `segment_tunnel_batch`, with `workspace_dev` holding
+/// `fragment_tunnel_workspace_bytes(batch.n)` bytes (16-byte aligned).
+pub unsafe fn fragment_tunnel_batch(batch: &ffi::rpkt_batch_t, outer_dev: *const Rec,
+                                    tun_dev: *const ffi::rpkt_tun_t, inner_dev: *const Rec,
+                                    mtu: u32, flags: u32, ip6_ident: u32, out: &SegmentOut,
+                                    workspace_dev: *mut core::ffi::c_void,
+                                    stream: *mut core::ffi::c_void) -> Result<(), Error> {
+    check(ffi::rpkt_gpu_fragment_tunnel_batch(batch, outer_dev, tun_dev, inner_dev, mtu, flags,
+                                              ip6_ident, out.frames_dev, out.out_bytes,
+                                              out.offsets_dev, out.out_cap, out.seg_first_dev,
+                                              out.totals_dev, workspace_dev, stream))
+}
+
 /// rpkt_gpu_reassemble_workspace_bytes: the workspace of reassemble_batch for `n` positions.
 pub fn reassemble_workspace_bytes(n: u32) -> usize {
     unsafe { ffi::rpkt_gpu_reassemble_workspace_bytes(n) }

@@ -122,6 +122,9 @@ enum rpkt_status {
  *   rpkt_gpu_fragment_chains: rpkt_gpu_segment_chains' order with frag_first_dev in
  *     seg_first_dev's place, flags other than 0 or RPKT_FRAGMENT_IGNORE_DF, then mtu outside
  *     1..65535 in mss's place;
+ *   rpkt_gpu_fragment_tunnel_batch: rpkt_gpu_segment_tunnel_batch's order with frag_first_dev
+ *     in seg_first_dev's place, flags with a bit other than RPKT_FRAGMENT_IGNORE_DF and
+ *     RPKT_FRAGMENT_TUNNEL_OUTER, then mtu outside 1..65535 in mss's place;
  *   rpkt_gpu_coalesce_batch: rpkt_gpu_segment_batch's order with src_first_dev in
  *     seg_first_dev's place (order_dev and out_mss_dev may be NULL), flags with a bit other
  *     than RPKT_COALESCE_TRUST_SUMS and RPKT_COALESCE_UDP, then max_payload outside 1..65535 in
@@ -1056,8 +1059,9 @@ int rpkt_gpu_segment_tunnel_chains(const rpkt_chains_t* chains, const rpkt_rec_t
  * fragmented, which is what a VTEP does with an encapsulation that is over the MTU.
  * Argument checks: rpkt_gpu_segment_batch's in its order (at enum rpkt_err).
  * Over mbuf chains: rpkt_gpu_fragment_chains, below.
- * Not covered: fragmenting the inner packet of a tunnel; an MTU per frame.  The receive-side
- * inverse is rpkt_gpu_reassemble_batch, below. */
+ * Fragmenting the INNER packet of a tunnel instead: rpkt_gpu_fragment_tunnel_batch, below.
+ * Not covered: an MTU per frame.  The receive-side inverse is rpkt_gpu_reassemble_batch,
+ * below. */
 #define RPKT_FRAGMENT_IGNORE_DF 1u   /* cut IPv4 packets that have DF set, too */
 
 size_t rpkt_gpu_fragment_workspace_bytes(uint32_t n);
@@ -1119,6 +1123,87 @@ int rpkt_gpu_fragment_chains(const rpkt_chains_t* chains, const rpkt_rec_t* recs
                              uint32_t* out_offsets_dev, uint32_t out_cap,
                              uint32_t* frag_first_dev, uint64_t* totals_dev,
                              void* workspace_dev, void* stream);
+
+/* Fragmenting the inner packet of a tunnel.  An encapsulation that is over the MTU can leave as
+ * fragments of the OUTER packet (rpkt_gpu_fragment_batch with the outer records), which makes
+ * the tunnel egress reassemble before it can decapsulate, leaves only the first fragment with
+ * the outer UDP header (ECMP and RSS spread one datagram's fragments) and is dropped by many
+ * middleboxes (RFC 4459 section 3.1, RFC 2003 section 5.1).  rpkt_gpu_fragment_tunnel_batch
+ * fragments the inner IPv4 packet before the encapsulation instead (RFC 4459 section 3.2; the
+ * "pre-fragmentation" of GRE / IPsec routers): every output is a complete tunnel packet with
+ * its own outer headers that is decapsulated on its own, and the destination host reassembles.
+ *
+ * outer_dev, tun_dev, inner_dev: the three outputs of rpkt_gpu_parse_tunnel_batch on this
+ * batch (level 1).  They only locate things; every header byte is read from the frame.  mtu,
+ * 1..65535: the L3 MTU of the link the OUTER packet leaves on.  flags: any combination of
+ * RPKT_FRAGMENT_IGNORE_DF and RPKT_FRAGMENT_TUNNEL_OUTER.  With O, T, I frame i's outer, tunnel
+ * and inner record:
+ *   1. No tunnel (T.kind == RPKT_TUN_NONE): the frame is handled exactly as
+ *      rpkt_gpu_fragment_batch handles it with record O and the same mtu, IGNORE_DF and
+ *      ip6_ident: its IPv4 and its IPv6 rule.  A mixed transmit batch needs one call.
+ *   2. Inner cut.  Let over = I.l3_off - O.l3_off: everything the tunnel puts in front of the
+ *      inner IP header, from the outer IP header through the inner Ethernet header and tags.
+ *      The frame is inner-cut iff T.status == RPKT_T_OK; the carrier is one
+ *      rpkt_gpu_segment_tunnel_batch accepts (outer IPv4 or IPv6 and not itself a fragment;
+ *      VXLAN / GTP-U: O.status OK, protocol 17, l4 + 8 <= tun_off; GRE: protocol 47, l4 ==
+ *      tun_off, S and R clear, room for the C word; tun_off + 8 (GRE: + 4, with C + 8) <=
+ *      inner_off <= I.l3_off); I's dispatch ethertype is 0x0800 and I.status is one under which
+ *      the IPv4 header parsed (rpkt_gpu_fragment_batch's list); mtu > over; and
+ *      rpkt_gpu_fragment_batch's IPv4 rule says "cut" for the inner packet at mtu' = mtu -
+ *      over with l3 = I.l3_off, l4 = I.l4_off and the outer frame's frame_len (l4 == l3 + ihl;
+ *      l3 + L <= frame_len; L > mtu'; DF clear or IGNORE_DF; c = (mtu' - ihl) & ~7 >= 8; the
+ *      13-bit offset does not overflow).  An inner packet that is already a fragment is cut
+ *      again.  Fragment k, with p_k as in that rule and tot = I.l4_off + p_k:
+ *        bytes        [0, I.l4_off) of the frame, then [I.l4_off + k * c, + p_k); nothing after
+ *                     the inner IP packet's end is carried;
+ *        inner IPv4   exactly what rpkt_gpu_fragment_batch writes for the inner packet on its
+ *                     own: packet_len, the frag word (offset, MF; DF and reserved 0),
+ *                     ip_options_fragment's NOOPs in fragments k > 0, the header checksum; the
+ *                     inner L4 bytes are untouched;
+ *        outer        exactly what rpkt_gpu_segment_tunnel_batch writes for an output of total
+ *                     length tot: the GTP-U length, the GRE checksum with C (0 stays 0), the
+ *                     outer UDP length and checksum (an input field of 0 stays 0; otherwise
+ *                     filled over the pseudo header, ip6_pdst_off rule, 0 -> 0xffff), the outer
+ *                     IPv4 packet_len, ident + k and checksum, or the outer IPv6 payload_len.
+ *                     The outer DF is copied: every output fits the link.  Length fields are
+ *                     taken mod 2^16.
+ *      Every output's outer IP packet is therefore at most mtu bytes long.
+ *   3. Everything else with a tunnel (kind != NONE: a tunnel that did not decode; inner IPv6,
+ *      which a tunnel ingress never fragments, RFC 8200 section 5 and RFC 2473 section 7.1;
+ *      inner DF without the flag; GRE with S or R; offsets that do not nest; an inner packet
+ *      that fits).  Without RPKT_FRAGMENT_TUNNEL_OUTER the frame passes through as a byte copy
+ *      of [0, frame_len): the caller owes an ICMP "fragmentation needed" / "packet too big".
+ *      With the flag it is handled as in rule 1 with record O: the outer packet is fragmented
+ *      if that rule cuts it.
+ * ip6_ident + i is used by rules 1 and 3 only.
+ * The outputs, frag_first_dev, totals_dev, the overflow behaviour, the spare offset slots and
+ * "nothing written outside the buffers" are rpkt_gpu_fragment_batch's, word for word; every
+ * load goes through the frames buffer resource and every store through the output's, so wrong
+ * records give wrong frames, never a fault.  The call is plan, prefix sums and write on
+ * `stream` with no host step: rpkt_gpu_parse_tunnel_batch -> rpkt_gpu_fragment_tunnel_batch ->
+ * rpkt_gpu_parse_tunnel_batch over out_cap slots captures as one graph.
+ * workspace_dev: rpkt_gpu_fragment_tunnel_workspace_bytes(n) bytes (a 64-byte plan a frame),
+ * 16-byte aligned; calls that share one must be ordered.
+ * Bounds for sizing: n_out <= n + floor(frames_bytes / max(8, cmin)), cmin = (mtu - A) & ~7, A
+ * the longest per-fragment prefix from the outer L3 on: over + ihl for an inner cut,
+ * rpkt_gpu_fragment_batch's A + 8 otherwise.  out_bytes_needed <= frames_bytes + (n_out - n) *
+ * H, H the longest copied header: I.l4_off for an inner cut, rpkt_gpu_fragment_batch's H
+ * otherwise.
+ * Argument checks: rpkt_gpu_segment_tunnel_batch's in its order, with mtu in mss's place and
+ * the two flags (at enum rpkt_err).
+ * Not covered: mbuf chains; nested tunnels (only the level-1 records are accepted); an MTU per
+ * frame; inner IPv6; GRE sequence numbers.  Reassembling the inner packet at the tunnel egress
+ * is not built and not needed: the destination host reassembles. */
+#define RPKT_FRAGMENT_TUNNEL_OUTER 2u  /* a tunnelled frame whose inner packet is not cut: cut its outer packet */
+
+size_t rpkt_gpu_fragment_tunnel_workspace_bytes(uint32_t n);
+int rpkt_gpu_fragment_tunnel_batch(const rpkt_batch_t* batch, const rpkt_rec_t* outer_dev,
+                                   const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                   uint32_t mtu, uint32_t flags, uint32_t ip6_ident,
+                                   uint8_t* out_frames_dev, uint64_t out_bytes,
+                                   uint32_t* out_offsets_dev, uint32_t out_cap,
+                                   uint32_t* frag_first_dev, uint64_t* totals_dev,
+                                   void* workspace_dev, void* stream);
 
 /* ---- IPv4 / IPv6 reassembly --------------------------------------------------------- */
 

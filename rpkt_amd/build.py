@@ -139,7 +139,7 @@ def build_gen(force=False):
 
 EXAMPLES = ("parse_batch", "flow_reduce", "rx_graph", "vtep_rx", "tso_tx", "tso_tx_chains", "lro_rx",
             "vtep_tx", "vtep_gro_rx", "vtep_tx_chains", "vtep_frag_tx", "vtep_frag_rx",
-            "frag_tx_chains")
+            "frag_tx_chains", "vtep_prefrag_tx")
 EXAMPLE_BIN = os.path.join(ROOT, "examples", "parse_batch")
 FLOW_REDUCE_BIN = os.path.join(ROOT, "examples", "flow_reduce")
 VTEP_RX_BIN = os.path.join(ROOT, "examples", "vtep_rx")
@@ -152,6 +152,7 @@ VTEP_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "vtep_tx_chains")
 VTEP_FRAG_TX_BIN = os.path.join(ROOT, "examples", "vtep_frag_tx")
 VTEP_FRAG_RX_BIN = os.path.join(ROOT, "examples", "vtep_frag_rx")
 FRAG_TX_CHAINS_BIN = os.path.join(ROOT, "examples", "frag_tx_chains")
+VTEP_PREFRAG_TX_BIN = os.path.join(ROOT, "examples", "vtep_prefrag_tx")
 
 
 def build_example(force=False):

@@ -38,6 +38,10 @@
 // templated on the header reader.  The write copies each slice as one wave copy per segment it
 // touches and carries its place in the segment list from one fragment of a chain to the next:
 // slices ascend, so the cursor only moves forward.
+//
+// rpkt_gpu_fragment_tunnel_batch cuts the inner IPv4 packet of a tunnelled frame before the
+// encapsulation: the IPv4 rule above with the inner record, the outer headers as tunnel
+// segmentation writes them ("tunnels" below has the description).
 #include "rpkt_chaincopy.h"
 
 namespace {
@@ -457,9 +461,202 @@ void fragment_chains_write_kernel(const uint8_t* __restrict__ buf, uint32_t fb,
     }
 }
 
+// ---- tunnels: the inner IPv4 packet of VXLAN, GTP-U and GRE frames ------------------------
+//
+// rpkt_gpu_fragment_tunnel_batch cuts the inner IPv4 packet of a decoded tunnel before the
+// encapsulation (RFC 4459 section 3.2): the inner record's offsets are positions in the outer
+// frame, so the cut is plan_ip4 with the inner record at mtu - over (over: the bytes from the
+// outer IP header to the inner one), the copied header is [0, inner l4_off), and the outer
+// headers follow as rpkt_gpu_segment_tunnel_batch writes them.  The plan is 64 B a frame: words
+// 0..7 as above for the packet that is cut (the inner one; the frame's own for a frame without
+// a tunnel or, with RPKT_FRAGMENT_TUNNEL_OUTER, one whose inner packet is not cut), then words
+// 8..11 and the kTun* bits of word 7 as rpkt_segment.hip ("tunnels") has them.
+// The constant under the outer checksum (word 11) must not depend on k, and the inner header's
+// packet_len, frag word, checksum and NOOP-ed options do.  The rule, once: a filled IPv4 header
+// sums to 0xffff, which is 0 in one's complement, at either parity; so the constant is the
+// pseudo header and [origin, inner l3) without the outer fields the write patches, the inner
+// header [inner l3, inner l4) adds nothing, and the slice's sum enters at the parity of inner
+// l4 - origin.  (What is summed is never all zero -- the pseudo header's 17, GRE's protocol --
+// so the sum stays in the class of the full one and 0 / 0xffff come out as they would.)  The
+// slice is summed in its copy, wave_copy<true>, only where the outer checksum is filled
+// (kTunCsum); every other output goes through wave_copy<false> as the flat write's.
+
+__global__ __launch_bounds__(kSegBlock)
+void fragment_tunnel_plan_kernel(const uint8_t* __restrict__ frames, uint32_t fb,
+                                 const uint32_t* __restrict__ offsets, uint32_t stride,
+                                 uint32_t frame_len, uint32_t n, const rpkt_rec_t* __restrict__ outer,
+                                 const rpkt_tun_t* __restrict__ tun, const rpkt_rec_t* __restrict__ inner,
+                                 uint32_t mtu, uint32_t ignore_df, uint32_t outer_fallback,
+                                 uint32_t ip6_ident, u32x4* __restrict__ plan,
+                                 uint32_t* __restrict__ frag_first, uint64_t* __restrict__ obase,
+                                 uint64_t* __restrict__ part) {
+    __shared__ uint32_t stage[kWavesPerBlock][kWave * 21];
+    __shared__ uint64_t red[2 * kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t p0 = blockIdx.x * kSegBlock + wave * kWave;
+    const uint32_t i = p0 + lane;
+    const bool valid = i < n;
+    uint64_t cnt = 0, bytes = 0;
+    uint32_t p[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, q[4] = {0u, 0u, 0u, 0u};
+
+    if (p0 < n) {                                                 // wave-uniform
+        // the tile's outer records through the stage, then its inner records through the same
+        uint32_t* st = stage[wave];
+        const uint32_t* w = st + lane * 21;
+        stage_records_tile(st, outer, p0, n, lane);
+        const uint32_t o0 = w[0], o5 = w[5], o7 = w[7], o8 = w[8], o16 = w[16];
+        const FragWhere fo = frag_where(w);
+        wave_sync();
+        stage_records_tile(st, inner, p0, n, lane);
+        const u32x4 t = valid ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tun) + i)
+                              : u32x4{0u, 0u, 0u, 0u};
+        const Frame fr = valid ? frame_span(offsets, stride, frame_len, fb, i) : Frame{0u, 0u};
+        p[0] = fr.off;
+        p[1] = fr.len;
+        if (valid) {
+            cnt = 1;
+            bytes = fr.len;
+            const FlatHeader H{make_rsrc(frames, fb), fb, fr.off};
+            // no tunnel: the frame's own packet under its outer record; so is a tunnelled frame
+            // whose inner packet is not cut, when the caller asks for it
+            bool own = (t.x & 0xffu) == RPKT_TUN_NONE;
+            if (!own) {
+                const FragWhere fi = frag_where(w);
+                L4Where in{};
+                in.l3 = fi.l3;
+                const TunWhere tw = tun_where(o0, o5, o7, o8, o16, t, in);
+                const uint32_t over = fi.l3 - tw.l3;              // tw.ok: outer l3 <= inner l3
+                uint32_t bits = 0;
+                // the cut is decided first: a frame whose inner packet fits or has DF set (most
+                // of a transmit batch) does not pay for the outer constants
+                bool cut = ((t.x >> 8) & 0xffu) == RPKT_T_OK && tw.ok && fi.v4 && mtu > over &&
+                           plan_ip4(H, fi.l3, fi.l4, fr.len, mtu - over, ignore_df != 0u, p, cnt,
+                                    bytes);
+                if (cut && !tunnel_constants_to(H, tw, fi.l3, q, bits, [](auto) {})) {
+                    // the GRE header forbids it after all: the plan as it was before plan_ip4
+                    cut = false;
+                    p[2] = p[3] = p[4] = p[5] = p[6] = p[7] = 0u;
+                    q[0] = q[1] = q[2] = q[3] = 0u;
+                    cnt = 1;
+                    bytes = fr.len;
+                }
+                if (cut) p[7] |= bits;
+                else own = outer_fallback != 0u;
+            }
+            if (own) {
+                if (fo.v4)
+                    plan_ip4(H, fo.l3, fo.l4, fr.len, mtu, ignore_df != 0u, p, cnt, bytes);
+                else if (fo.v6)
+                    plan_ip6(H, fo.l3, fo.l4, fr.len, mtu, ip6_ident + i, p, cnt, bytes);
+            }
+        }
+    }
+    if (valid) {
+        plan[4 * (size_t)i + 2] = u32x4{q[0], q[1], q[2], q[3]};
+        plan[4 * (size_t)i + 3] = u32x4{0u, 0u, 0u, 0u};
+    }
+    plan_store<4>(valid, i, p, cnt, bytes, plan, frag_first, obase, part, red);
+}
+
+// write_fragment for the 64-B plan (pa, pb, pc): an inner cut's fragment k, everything else as
+// the flat write has it
+__device__ __forceinline__ void write_tunnel_fragment(__amdgpu_buffer_rsrc_t rs, uint32_t fb,
+                                                      __amdgpu_buffer_rsrc_t ro,
+                                                      uint32_t* __restrict__ out_offsets, uint32_t j,
+                                                      uint32_t k, u32x4 pa, u32x4 pb, u32x4 pc,
+                                                      uint32_t base, int lane) {
+    if (!(pb.w & kTunOn)) {                                       // wave-uniform
+        write_fragment(rs, fb, ro, out_offsets, j, k, pa, pb, base, lane);
+        return;
+    }
+    const uint32_t foff = pa.x;
+    SegPatch Pt[kFragPatches];
+    const FragOut o = frag_out(pa, pb, k, base, Pt);              // the inner IPv4 rule: H == hs
+    if (lane == 0) out_offsets[j + 1] = o.d0 + o.H + o.pk;
+    auto fetch = [&](uint32_t c) -> uint32_t {
+        return noop_dword(o, c, header_dword(rs, fb, foff, o.d0, c));
+    };
+    const uint32_t hfirst = fetch((uint32_t)lane);
+    uint32_t pay = 0;
+    if (pb.w & kTunCsum) {                                        // wave-uniform
+        const uint32_t part = wave_copy<true>(rs, fb, ro, foff + o.hs + o.done, o.d0 + o.H, o.pk, lane);
+        pay = be_sum(wave_sum(fold16(part)), o.d0 + o.H);
+    } else {
+        wave_copy<false>(rs, fb, ro, foff + o.hs + o.done, o.d0 + o.H, o.pk, lane);
+    }
+    // the outer patches over an output whose payload starts at inner l4; no inner patch enters
+    // the outer sum (the rule above), so they are set after it is formed
+    SegPatch P[kTunPatches];
+#pragma unroll
+    for (int u = 0; u < kSegPatches; ++u) P[u] = SegPatch{0u, 0u, 0u};
+    const SegOut so{false, false, o.l3, o.hs, o.hs, o.done, o.pk, o.d0};
+    tunnel_patches(so, pb, pc, k, pay, P);
+#pragma unroll
+    for (int u = 0; u < 3; ++u) P[u] = Pt[u];
+    wave_copy_header_from(ro, o.d0, o.H, hfirst, P, lane, fetch);
+}
+
+__global__ __launch_bounds__(kSegBlock)
+void fragment_tunnel_write_kernel(const uint8_t* __restrict__ frames, uint32_t fb, uint32_t n,
+                                  const u32x4* __restrict__ plan,
+                                  const uint32_t* __restrict__ frag_first,
+                                  const uint64_t* __restrict__ obase,
+                                  const uint64_t* __restrict__ totals, uint8_t* __restrict__ out,
+                                  uint32_t out_bytes, uint32_t* __restrict__ out_offsets,
+                                  uint32_t out_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t j0, jend, i;
+    if (!output_run(n, frag_first, totals, out_bytes, out_offsets, out_cap, lane, j0, jend, i)) return;
+    uint32_t cur = frag_first[i], nxt = frag_first[i + 1];
+    u32x4 pa = plan[4 * (size_t)i], pb = plan[4 * (size_t)i + 1], pc = plan[4 * (size_t)i + 2];
+    uint32_t base = (uint32_t)obase[i];                           // < need <= out_bytes < 4 GiB
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(frames, fb);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, out_bytes);
+    for (uint32_t j = j0; j < jend; ++j) {
+        if (j >= nxt) {                                           // the next frame's first output
+            while (j >= nxt && i + 1u < n) {
+                ++i;
+                cur = nxt;
+                nxt = frag_first[i + 1];
+            }
+            pa = plan[4 * (size_t)i];
+            pb = plan[4 * (size_t)i + 1];
+            pc = plan[4 * (size_t)i + 2];
+            base = (uint32_t)obase[i];
+        }
+        write_tunnel_fragment(rs, fb, ro, out_offsets, j, j - cur, pa, pb, pc, base, lane);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t rpkt_gpu_fragment_tunnel_workspace_bytes(uint32_t n) { return seg_ws(nullptr, n, 4).bytes; }
+
+int rpkt_gpu_fragment_tunnel_batch(const rpkt_batch_t* b, const rpkt_rec_t* outer_dev,
+                                   const rpkt_tun_t* tun_dev, const rpkt_rec_t* inner_dev,
+                                   uint32_t mtu, uint32_t flags, uint32_t ip6_ident,
+                                   uint8_t* out_frames_dev, uint64_t out_bytes,
+                                   uint32_t* out_offsets_dev, uint32_t out_cap,
+                                   uint32_t* frag_first_dev, uint64_t* totals_dev,
+                                   void* workspace_dev, void* stream) {
+    RPKT_TRY(reframe_args_ok(b, outer_dev, mtu, flags,
+                             RPKT_FRAGMENT_IGNORE_DF | RPKT_FRAGMENT_TUNNEL_OUTER, out_frames_dev,
+                             out_bytes, out_offsets_dev, out_cap, frag_first_dev, totals_dev,
+                             workspace_dev, tun_dev, inner_dev));
+    if (b->n == 0) return RPKT_OK;
+
+    const SegWs ws = seg_ws(workspace_dev, b->n, 4);
+    RPKT_TRY(launch_batch(fragment_tunnel_plan_kernel, kSegBlock, 0, stream, *b, outer_dev, tun_dev,
+                          inner_dev, mtu, flags & RPKT_FRAGMENT_IGNORE_DF,
+                          flags & RPKT_FRAGMENT_TUNNEL_OUTER, ip6_ident, ws.plan, frag_first_dev,
+                          ws.obase, ws.part));
+    return scan_and_write(fragment_tunnel_write_kernel, ws, b->n, out_cap, frag_first_dev,
+                          totals_dev, (hipStream_t)stream, b->frames_dev,
+                          (uint32_t)b->frames_bytes, b->n, ws.plan, frag_first_dev, ws.obase,
+                          totals_dev, out_frames_dev, (uint32_t)out_bytes, out_offsets_dev, out_cap);
+}
 
 size_t rpkt_gpu_fragment_workspace_bytes(uint32_t n) { return seg_ws(nullptr, n).bytes; }
 

@@ -553,8 +553,9 @@ int scan_and_write(void (*write_kernel)(KArgs...), const SegWs& ws, uint32_t n, 
 
 // ---- tunnels: the carrier of an inner TCP / UDP frame -----------------------------------
 //
-// What rpkt_gpu_segment_tunnel_batch (rpkt_segment.hip, "tunnels") and
-// rpkt_gpu_coalesce_tunnel_batch (rpkt_coalesce.hip) share: the bits that say which outer
+// What rpkt_gpu_segment_tunnel_batch (rpkt_segment.hip, "tunnels"),
+// rpkt_gpu_coalesce_tunnel_batch (rpkt_coalesce.hip) and rpkt_gpu_fragment_tunnel_batch
+// (rpkt_fragment.hip, "tunnels": the carrier of an inner IPv4 packet) share: the bits that say which outer
 // headers a frame has, the rule for a carrier whose headers can be fixed up, the constants of
 // its outer checksums and the outer patches of an output.
 constexpr uint32_t kTunOn = 8u, kTunV6 = 16u, kTunUdp = 32u, kTunGtp = 64u, kTunCsum = 128u;
@@ -586,13 +587,15 @@ __device__ __forceinline__ TunWhere tun_where(uint32_t w0, uint32_t w5, uint32_t
     return TunWhere{ok, v6, !gre, gtp, l3, l4, toff, ioff, pdst};
 }
 
-// Plan words 8..11 (q[0..3]) and the tunnel bits of word 7 for a frame whose inner frame `s` is
+// Plan words 8..11 (q[0..3]) and the tunnel bits of word 7 for a frame whose inner packet is
 // cut; false when the GRE header forbids it (the S or R bit, or C without room for its word).
-template <class Header>
-__device__ __forceinline__ bool tunnel_constants(const Header& H, const L4Where& s,
-                                                 const TunWhere& w, uint32_t (&q)[4],
-                                                 uint32_t& bits) {
-    const uint32_t l3 = w.l3, l4 = w.l4, toff = w.toff, po = s.po;
+// The constant under the outer checksum is [origin, end) without the outer fields the write
+// patches and without what `inner(drop)` drops: the inner fields the caller's write patches.
+template <class Header, class InnerDrops>
+__device__ __forceinline__ bool tunnel_constants_to(const Header& H, const TunWhere& w,
+                                                    uint32_t end, uint32_t (&q)[4],
+                                                    uint32_t& bits, InnerDrops inner) {
+    const uint32_t l3 = w.l3, l4 = w.l4, toff = w.toff, po = end;
     bool csum;
     uint32_t origin, c = 0;
     if (w.udp) {
@@ -621,17 +624,7 @@ __device__ __forceinline__ bool tunnel_constants(const Header& H, const L4Where&
         };
         if (w.udp) drop(l4 + 4u, 4u); else drop(toff + 4u, 2u);
         if (w.gtp) drop(toff + 2u, 2u);
-        if (s.v6) {
-            drop(s.l3 + 4u, 2u);
-        } else {
-            drop(s.l3 + 2u, 4u);
-            drop(s.l3 + 10u, 2u);
-        }
-        drop(s.l4 + 4u, 4u);
-        if (!s.udp) {
-            drop(s.l4 + 13u, 1u);
-            drop(s.l4 + 16u, 2u);
-        }
+        inner(drop);
     }
     uint32_t opc = 0, oident = 0;
     if (!w.v6) {
@@ -646,6 +639,28 @@ __device__ __forceinline__ bool tunnel_constants(const Header& H, const L4Where&
     bits = kTunOn | (w.v6 ? kTunV6 : 0u) | (w.udp ? kTunUdp : 0u) | (w.gtp ? kTunGtp : 0u) |
            (csum ? kTunCsum : 0u);
     return true;
+}
+
+// The same for a frame whose inner TCP / UDP frame `s` is segmented or merged: the constant
+// runs to the inner payload and drops the inner IP length (IPv4: and ident, checksum), and the
+// L4 fields seg_patches writes.
+template <class Header>
+__device__ __forceinline__ bool tunnel_constants(const Header& H, const L4Where& s,
+                                                 const TunWhere& w, uint32_t (&q)[4],
+                                                 uint32_t& bits) {
+    return tunnel_constants_to(H, w, s.po, q, bits, [&](auto drop) {
+        if (s.v6) {
+            drop(s.l3 + 4u, 2u);
+        } else {
+            drop(s.l3 + 2u, 4u);
+            drop(s.l3 + 10u, 2u);
+        }
+        drop(s.l4 + 4u, 4u);
+        if (!s.udp) {
+            drop(s.l4 + 13u, 1u);
+            drop(s.l4 + 16u, 2u);
+        }
+    });
 }
 
 // The outer headers' patches of output k, P[5..8], after the inner ones P[0..4]; pc: plan

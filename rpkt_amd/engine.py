@@ -98,6 +98,9 @@ ABI = {
     "rpkt_gpu_fragment_chains_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_fragment_chains": (_i, [_C, _p, _u32, _u32, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p,
                                       _p, _p]),
+    "rpkt_gpu_fragment_tunnel_workspace_bytes": (_sz, [_u32]),
+    "rpkt_gpu_fragment_tunnel_batch": (_i, [_B, _p, _p, _p, _u32, _u32, _u32, _p, ctypes.c_uint64, _p,
+                                            _u32, _p, _p, _p, _p]),
     "rpkt_gpu_reassemble_workspace_bytes": (_sz, [_u32]),
     "rpkt_gpu_reassemble_batch": (_i, [_B, _p, _p, _u32, _p, ctypes.c_uint64, _p, _u32, _p, _p, _p,
                                        _p]),
@@ -835,6 +838,51 @@ def fragment_chains(chains, recs, mtu, ignore_df=False, ip6_ident=0, out_frames=
     return _fragment("rpkt_gpu_fragment_chains", chains, "fragment_chains", recs, mtu, ignore_df,
                      ip6_ident, out_frames, out_offsets, out_cap, out_bytes, frag_first, totals,
                      workspace, l3_header_max, stream)
+
+
+FRAGMENT_TUNNEL_OUTER = 2
+
+
+def fragment_tunnel_workspace(n, device="cuda"):
+    """The workspace tensor of fragment_tunnel_batch for n input frames
+    (rpkt_gpu_fragment_tunnel_workspace_bytes)."""
+    return _workspace("fragment_tunnel", n, device)
+
+
+def fragment_tunnel_batch(batch, outer, tun, inner, mtu, ignore_df=False, outer_fallback=False,
+                          ip6_ident=0, out_frames=None, out_offsets=None, out_cap=None,
+                          out_bytes=None, frag_first=None, totals=None, workspace=None, stream=None,
+                          header_max=None):
+    """rpkt_gpu_fragment_tunnel_batch: fragmentation of the inner IPv4 packet of the VXLAN /
+    GTP-U / GRE frames of `batch` before the encapsulation (RFC 4459 section 3.2), so that every
+    output's OUTER IP packet is at most `mtu` bytes and carries outer headers of its own;
+    `outer`, `tun`, `inner` are parse_tunnel_batch's three tensors for this batch.  A frame
+    without a tunnel is cut as fragment_batch cuts it with its outer record; a tunnelled frame
+    whose inner packet is not cut passes through, or with outer_fallback
+    (RPKT_FRAGMENT_TUNNEL_OUTER) has its outer packet cut as fragment_batch would.  ignore_df and
+    ip6_ident as for fragment_batch.  Returns (out, frag_first, totals) under fragment_batch's
+    overflow rule.
+    By default the outputs are sized from the documented bound with header_max, the longest
+    copied header of the batch (an inner cut's inner l4_off; l4_off or U + 8 otherwise), 272
+    unless given (segment_tunnel_batch's allowance): out_cap = n + frames_bytes //
+    max(8, (mtu - header_max) & ~7) slots -- header_max also bounds the per-fragment prefix from
+    the outer L3 on -- and out_bytes = frames_bytes + (out_cap - n) * header_max bytes."""
+    n, fbytes = batch.n, batch.frames.numel()
+    hmax = 272 if header_max is None else header_max
+    out_frames, out_bytes, out_offsets, out_cap, frag_first, totals, workspace = _reframe_outputs(
+        "fragment_tunnel_batch", batch, outer,
+        lambda: n + fbytes // max(8, (mtu - hmax) & ~7 if mtu > hmax else 0),
+        lambda cap: fbytes + (cap - n) * hmax,
+        out_frames, out_offsets, out_cap, out_bytes, frag_first, "frag_first", totals, workspace,
+        "fragment_tunnel")
+    if tun.numel() != n * 16 or inner.numel() != n * REC_BYTES:
+        raise RpktError("fragment_tunnel_batch: tunnel or inner records do not fit %d frames" % n)
+    flags = (FRAGMENT_IGNORE_DF if ignore_df else 0) | (FRAGMENT_TUNNEL_OUTER if outer_fallback else 0)
+    _call("rpkt_gpu_fragment_tunnel_batch", ctypes.byref(batch.desc()), outer.data_ptr(),
+          tun.data_ptr(), inner.data_ptr(), mtu, flags, ip6_ident & 0xffffffff,
+          out_frames.data_ptr(), out_bytes, out_offsets.data_ptr(), out_cap, frag_first.data_ptr(),
+          totals.data_ptr(), workspace.data_ptr(), _stream_ptr(stream))
+    return DeviceBatch(out_frames, out_cap, out_offsets), frag_first, totals
 
 
 REASSEMBLE_TRUST_SUMS = 1

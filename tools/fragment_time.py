@@ -25,7 +25,23 @@ the records from rpkt_gpu_parse_chains, in the same interleaved rounds as
 Recorded: `chains_over_flatten_then_fragment`, t(fragment_chains) / (t(device_copy) +
 t(fragment_batch)): what a caller without the entry must do; `chains_over_fragment_batch`; and
 `chains_over_segment_chains_per_output_byte`.  The chains' output must equal the flat entry's
-byte for byte, and passes the same checks."""
+byte for byte, and passes the same checks.
+
+    python tools/fragment_time.py --tunnel [--out profiles/fragment/tunnel_times.json]
+times rpkt_gpu_fragment_tunnel_batch: the same datagrams behind segment_time.vxlan_prefix (50
+bytes from the outer IP header to the inner one, so the inner packet is cut at mtu' 1450 into
+slices of 1424 bytes: 24 tunnel packets a frame where the flat cut at 1480 gives 23), once with
+a filled and once with a zero outer UDP checksum, in the same interleaved rounds as
+  fragment_outer       rpkt_gpu_fragment_batch with the outer records on the same frames: what a
+                       caller does without the entry (23 fragments of the OUTER packet);
+  segment_tunnel_udp   rpkt_gpu_segment_tunnel_batch with RPKT_SEGMENT_UDP at mss 1424, the same
+                       slice: the same copy, payload sum and outer patches, and an inner L4
+                       checksum that fragmentation does not have;
+  device_copy          a copy of one batch's bytes.
+Recorded for each variant: `tunnel_over_segment_tunnel_udp_per_output_byte`,
+`tunnel_over_fragment_outer_per_output_byte` and `tunnel_over_copy_per_byte`.  The same run
+checks the output: the outputs a frame, every outer packet within the mtu, and a tunnel parse of
+the output with every tunnel decoded and every sum valid."""
 import argparse
 import json
 import os
@@ -37,8 +53,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from segment_time import (HBM_BYTES_PER_S, PAYLOAD, UDP_HDR, mbuf_chains, rfc1071, time_legs,  # noqa: E402
-                          udp_super_frames)
+from segment_time import (HBM_BYTES_PER_S, PAYLOAD, TUN_HDR, UDP_HDR, mbuf_chains, rfc1071,  # noqa: E402
+                          time_legs, udp_super_frames, vxlan_prefix)
 
 MTU, MSS = 1500, 1472
 
@@ -55,15 +71,143 @@ def datagrams(n, seed):
     return f
 
 
+def vxlan_datagrams(n, seed):
+    """segment_time.vxlan_prefix around datagrams(): (n, 50 + 42 + 32768) uint8, the outer
+    lengths those of this inner frame, the outer DF clear (so that the outer packet can be cut
+    too) and the outer UDP checksum the prefix's non-zero placeholder."""
+    inner = datagrams(n, seed)
+    p = vxlan_prefix()
+    tot, ulen = 36 + inner.shape[1], 16 + inner.shape[1]
+    p[16:18] = (tot >> 8, tot & 255)
+    p[20:22] = 0
+    p[24:26] = 0
+    ck = rfc1071(p[14:34])
+    p[24:26] = (ck >> 8, ck & 255)
+    p[38:40] = (ulen >> 8, ulen & 255)
+    f = np.empty((n, TUN_HDR + inner.shape[1]), dtype=np.uint8)
+    f[:, :TUN_HDR] = p
+    f[:, TUN_HDR:] = inner
+    return f
+
+
+def tunnel_main(a):
+    """--tunnel: rpkt_gpu_fragment_tunnel_batch on VXLAN-wrapped datagrams, once with a filled
+    and once with a zero outer UDP checksum (the module docstring has the legs)."""
+    import torch
+    from rpkt_amd import engine
+    from rpkt_amd.records import as_records, as_tunnels
+
+    stream = torch.cuda.current_stream()
+    n, flen = a.n, TUN_HDR + UDP_HDR + PAYLOAD
+    over, il4 = TUN_HDR, TUN_HDR + 34                              # outer l3 to inner l3; inner l4_off
+    P, c = 8 + PAYLOAD, (MTU - over - 20) & ~7                      # the inner IP payload, the slice
+    per = -(-P // c)
+    mss = c                                                         # the same slice of UDP payload
+    seg_per, seg_hdr = -(-PAYLOAD // mss), TUN_HDR + UDP_HDR
+    oP, oc = flen - 34, (MTU - 20) & ~7                             # the outer cut of the same frame
+    o_per = -(-oP // oc)
+    need, seg_need, o_need = n * (per * il4 + P), n * (seg_per * seg_hdr + PAYLOAD), n * (o_per * 34 + oP)
+    dbs = [engine.DeviceBatch(torch.from_numpy(vxlan_datagrams(n, seed).reshape(-1)).to("cuda"), n,
+                              stride=flen) for seed in (53, 5353)]
+    R = len(dbs)
+    cap = n * max(per, seg_per, o_per)
+    outs = {k: (torch.empty(b, dtype=torch.uint8, device="cuda"),
+                torch.empty(cap + 1, dtype=torch.int32, device="cuda"),
+                torch.empty(n + 1, dtype=torch.int32, device="cuda"),
+                torch.zeros(2, dtype=torch.int64, device="cuda"))
+            for k, b in (("tunnel", need), ("segment", seg_need), ("outer", o_need))}
+    ws = {"tunnel": engine.fragment_tunnel_workspace(n), "segment": engine.segment_tunnel_workspace(n),
+          "outer": engine.fragment_workspace(n)}
+    res = {"device": engine.device_info(), "build": engine.lib().rpkt_gpu_build_info().decode(),
+           "frames": n, "frame_len": flen, "mtu": MTU, "mss": mss, "over": over,
+           "outputs_a_frame": {"fragment_tunnel": per, "segment_tunnel_udp": seg_per,
+                               "fragment_outer": o_per},
+           "bytes_out": {"fragment_tunnel": need, "segment_tunnel_udp": seg_need,
+                         "fragment_outer": o_need},
+           "batches_rotated": R, "launches_per_round": a.launches, "rounds": a.rounds}
+    for variant in ("filled", "zero"):
+        if variant == "zero":                                       # the outer UDP checksum field
+            for db in dbs:
+                db.frames.view(n, flen)[:, 40:42] = 0
+        recs = [engine.parse_tunnel_batch(db, 0) for db in dbs]
+
+        def call(fn, key, k, *args, **kw):
+            f, o, first, tot = outs[key]
+            fn(dbs[k % R], *args, out_frames=f, out_offsets=o, out_cap=cap, totals=tot,
+               workspace=ws[key], stream=stream, **kw)
+
+        def fragment_tunnel(k):
+            call(engine.fragment_tunnel_batch, "tunnel", k, *recs[k % R], MTU, frag_first=outs["tunnel"][2])
+
+        def fragment_outer(k):
+            call(engine.fragment_batch, "outer", k, recs[k % R][0], MTU, frag_first=outs["outer"][2])
+
+        def segment_tunnel_udp(k):
+            call(engine.segment_tunnel_batch, "segment", k, *recs[k % R], mss, udp=True,
+                 seg_first=outs["segment"][2])
+
+        def copy(k):
+            outs["tunnel"][0][:n * flen].copy_(dbs[k % R].frames)
+
+        legs = {"fragment_tunnel": fragment_tunnel, "fragment_outer": fragment_outer,
+                "segment_tunnel_udp": segment_tunnel_udp, "device_copy": copy}
+        med, ms = time_legs(torch, stream, legs, a.launches, a.rounds)
+
+        # the workload is what it claims: the outputs a frame, every outer packet within the
+        # mtu, and a tunnel parse of the output with every sum valid
+        fragment_tunnel(0), fragment_outer(0), segment_tunnel_udp(0)
+        torch.cuda.synchronize()
+        assert outs["tunnel"][3].cpu().tolist() == [n * per, need], outs["tunnel"][3].cpu().tolist()
+        assert outs["outer"][3].cpu().tolist() == [n * o_per, o_need], outs["outer"][3].cpu().tolist()
+        assert outs["segment"][3].cpu().tolist() == [n * seg_per, seg_need], outs["segment"][3].cpu().tolist()
+        assert np.array_equal(outs["tunnel"][2].cpu().numpy().view(np.uint32),
+                              np.arange(n + 1, dtype=np.uint32) * per)
+        odb = engine.DeviceBatch(outs["tunnel"][0], n * per, outs["tunnel"][1][:n * per + 1])
+        O, T, I = (view(t.cpu().numpy()) for t, view in
+                   zip(engine.parse_tunnel_batch(odb, 3), (as_records, as_tunnels, as_records)))
+        k = np.arange(n * per) % per
+        assert (T["status"] == 0).all() and (T["kind"] == 1).all()
+        assert (O["status"] == 0).all() and (O["ip_sum"] == 0xffff).all()
+        assert (O["l4_sum"] == 0xffff).all() if variant == "filled" else True
+        assert int(O["ip_packet_len"].max()) <= MTU and int(O["ip_packet_len"].max()) == over + 20 + c
+        assert (I["ip_sum"] == 0xffff).all() and (I["ip_protocol"] == 17).all()
+        assert np.array_equal(I["ip_frag"], (k * c // 8) | np.where(k < per - 1, 0x2000, 0))
+        assert (I["ip_packet_len"][k < per - 1] == 20 + c).all()
+        assert (I["ip_packet_len"][k == per - 1] == 20 + P - (per - 1) * c).all()
+
+        alg = n * flen + n * 176 + need + (n * per + 1) * 4
+        v = {"ms": {name: {"ms": round(t, 4), "rounds_ms": [round(x, 4) for x in ms[name]]}
+                    for name, t in med.items()}}
+        v["ms"]["fragment_tunnel"]["bytes"] = alg
+        v["ms"]["fragment_tunnel"]["fraction_of_8TBs"] = round(
+            alg / (med["fragment_tunnel"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        v["tunnel_over_segment_tunnel_udp_per_output_byte"] = round(
+            (med["fragment_tunnel"] / need) / (med["segment_tunnel_udp"] / seg_need), 4)
+        v["tunnel_over_fragment_outer_per_output_byte"] = round(
+            (med["fragment_tunnel"] / need) / (med["fragment_outer"] / o_need), 4)
+        v["tunnel_over_copy_per_byte"] = round(
+            (med["fragment_tunnel"] / alg) / (med["device_copy"] / (2 * n * flen)), 4)
+        res[variant + "_outer_udp_checksum"] = v
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--chains", action="store_true",
                     help="time rpkt_gpu_fragment_chains on the same datagrams as mbuf chains")
+    ap.add_argument("--tunnel", action="store_true",
+                    help="time rpkt_gpu_fragment_tunnel_batch on the same datagrams behind VXLAN")
     ap.add_argument("--n", type=int, default=32768)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
+    if a.tunnel:
+        a.out = a.out or "profiles/fragment/tunnel_times.json"
+        return tunnel_main(a)
     a.out = a.out or ("profiles/fragment/chains_times.json" if a.chains else
                       "profiles/fragment/times.json")
     import torch

@@ -37,7 +37,10 @@ rpkt_gpu_reassemble_batch (under engine.reassemble_order of the keys, or in arri
 or without TRUST_SUMS) against tests/reassemble_model.py; (h) a generator chain batch in the
 fuzz or the mbuf layout through rpkt_gpu_fragment_chains at a random mtu, flag and ip6_ident, with
 the chain parse's records or the flat ones of the flattened bytes, against
-tests/fragment_chains_model.py (the fragment model on the flattened chains).  Build and forward rewrite frames in place, so they run on generator batches
+tests/fragment_chains_model.py (the fragment model on the flattened chains); (i) a tunnel batch
+(config 13 / 14) through rpkt_gpu_fragment_tunnel_batch at a random mtu, random flags
+(RPKT_FRAGMENT_IGNORE_DF, RPKT_FRAGMENT_TUNNEL_OUTER) and a random ip6_ident against
+tests/fragment_tunnel_model.py (--only fragment_tunnel runs this step alone).  Build and forward rewrite frames in place, so they run on generator batches
 (the random layouts overlap frames on purpose)."""
 import argparse
 import json
@@ -59,6 +62,7 @@ from rpkt_amd.records import (F_FLOW_EV, F_IPV6, LAYERS_DTYPE, as_opts, as_recor
 import coalesce_tunnel_model  # noqa: E402
 import fragment_chains_model  # noqa: E402
 import fragment_model  # noqa: E402
+import fragment_tunnel_model  # noqa: E402
 import fuzz_layouts  # noqa: E402
 import nested_tunnel_ref  # noqa: E402
 import reassemble_model  # noqa: E402
@@ -480,8 +484,33 @@ def check_fragment_chains(rng, seed):
             "records": kind, "n_out": int(totals[0])}
 
 
+def check_fragment_tunnel(rng, seed):
+    """rpkt_gpu_fragment_tunnel_batch on a config 13 / 14 batch at a random mtu, random flags and
+    ip6_ident, against tests/fragment_tunnel_model.py."""
+    cfg = int(rng.choice([13, 14]))
+    hb = gen.make_batch(cfg, n=int(rng.integers(1, 3000)), seed=seed)
+    mtu = int(rng.choice([24, 51, 52, 64, 78, 100, 120, 300, 576, 1280, 1500, 65535]))
+    ignore_df, fallback = bool(rng.random() < 0.8), bool(rng.random() < 0.5)
+    ident = int(rng.integers(0, 1 << 32))
+    outer, tun, inner = fragment_tunnel_model.tunnel_records(hb)
+    out, first, totals = fragment_tunnel_model.fragment(hb, outer, tun, inner, mtu, ignore_df, fallback,
+                                                        ident)
+    out_cap = int(totals[0]) + int(rng.integers(0, 9))
+    db = engine.DeviceBatch.from_host(hb)
+    odb, gf, gt = engine.fragment_tunnel_batch(db, *engine.parse_tunnel_batch(db, segment_model.F6), mtu,
+                                               ignore_df, fallback, ident, out_cap=out_cap,
+                                               out_bytes=int(totals[1]) + int(rng.integers(0, 40)))
+    same_reframed("fragment_tunnel_batch", odb, gf, gt, out, first, totals, out_cap)
+    kinds, outer_cuts = fragment_tunnel_model.cut_kinds(
+        first, tun, fragment_tunnel_model.inner_cuts(hb, outer, tun, inner, mtu, ignore_df))
+    return {"cfg": cfg, "n": int(hb.n), "mtu": mtu, "ignore_df": ignore_df, "outer": fallback,
+            "n_out": int(totals[0]), "inner_cut": [kinds[k] for k in (1, 2, 3)], "outer_cut": outer_cuts}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default=None, choices=["fragment_tunnel"],
+                    help="run this step alone on every seed instead of the whole sweep")
     ap.add_argument("--minutes", type=float, default=8.0)
     ap.add_argument("--seed0", type=int, default=50000)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "parity_sweep.jsonl"))
@@ -495,35 +524,41 @@ def main():
             rec = {"seed": seed}
             step = "layout"
             try:
-                hb = (fuzz_layouts.packed_layout if rng.random() < 0.6 else
-                      fuzz_layouts.strided_layout)(rng, int(rng.integers(1, 5000)))
-                rec["layout"] = check_layout(hb, rng)
-                step = "tx"
-                rec["tx"] = check_tx(rng, seed)
-                step = "encap"
-                rec["encap"] = check_encap(rng, seed)
-                step = "chains"
-                rec["chains"] = check_chains(rng, seed)
-                step = "segment_chains"
-                rec["segment_chains"] = check_segment_chains(rng, seed)
-                step = "segment_coalesce"
-                rec["segment_coalesce"] = check_segment_coalesce(rng, seed)
-                step = "segment_tunnel"
-                rec["segment_tunnel"] = check_segment_tunnel(rng, seed)
-                step = "coalesce_tunnel"
-                rec["coalesce_tunnel"] = check_coalesce_tunnel(rng, seed)
-                step = "tunnel_chains"
-                rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
-                step = "tunnel_next"
-                rec["tunnel_next"] = check_tunnel_next(rng, seed)
-                step = "segment_tunnel_chains"
-                rec["segment_tunnel_chains"] = check_segment_tunnel_chains(rng, seed)
-                step = "fragment"
-                rec["fragment"] = check_fragment(rng, seed)
-                step = "reassemble"
-                rec["reassemble"] = check_reassemble(rng, seed)
-                step = "fragment_chains"
-                rec["fragment_chains"] = check_fragment_chains(rng, seed)
+                if args.only == "fragment_tunnel":
+                    step = "fragment_tunnel"
+                    rec[step] = check_fragment_tunnel(rng, seed)
+                else:
+                    hb = (fuzz_layouts.packed_layout if rng.random() < 0.6 else
+                          fuzz_layouts.strided_layout)(rng, int(rng.integers(1, 5000)))
+                    rec["layout"] = check_layout(hb, rng)
+                    step = "tx"
+                    rec["tx"] = check_tx(rng, seed)
+                    step = "encap"
+                    rec["encap"] = check_encap(rng, seed)
+                    step = "chains"
+                    rec["chains"] = check_chains(rng, seed)
+                    step = "segment_chains"
+                    rec["segment_chains"] = check_segment_chains(rng, seed)
+                    step = "segment_coalesce"
+                    rec["segment_coalesce"] = check_segment_coalesce(rng, seed)
+                    step = "segment_tunnel"
+                    rec["segment_tunnel"] = check_segment_tunnel(rng, seed)
+                    step = "coalesce_tunnel"
+                    rec["coalesce_tunnel"] = check_coalesce_tunnel(rng, seed)
+                    step = "tunnel_chains"
+                    rec["tunnel_chains"] = check_tunnel_chains(rng, seed)
+                    step = "tunnel_next"
+                    rec["tunnel_next"] = check_tunnel_next(rng, seed)
+                    step = "segment_tunnel_chains"
+                    rec["segment_tunnel_chains"] = check_segment_tunnel_chains(rng, seed)
+                    step = "fragment"
+                    rec["fragment"] = check_fragment(rng, seed)
+                    step = "reassemble"
+                    rec["reassemble"] = check_reassemble(rng, seed)
+                    step = "fragment_chains"
+                    rec["fragment_chains"] = check_fragment_chains(rng, seed)
+                    step = "fragment_tunnel"
+                    rec["fragment_tunnel"] = check_fragment_tunnel(rng, seed)
             except AssertionError as e:
                 rec.update(failed=step, error=str(e)[:400])
                 fh.write(json.dumps(rec) + "\n")
